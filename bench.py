@@ -9,8 +9,9 @@ N > 1: weak scaling, every rank owns a 400 x 160 x 160 slab of a 400 x 160 x (16
 Every warm-up and timed step restores the same device-side snapshot (state after two spin-up iterations) and runs one
 full SIMPLE iteration, so all steps do identical work (the reference algorithm itself diverges on this mesh).
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (CSR SpMV inside BiCGSTAB, HBM bound,
-measured live with HIP events on the library stream) and `cpu_baseline` (the CPU oracle = restatement of
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run sets up, warms up, times --steps steps and (with
+--dump-outputs DIR) writes what the last step computed; --full adds `roofline` (CSR SpMV inside BiCGSTAB, HBM bound,
+measured live with HIP events on the library stream), `amg_levels` and `cpu_baseline` (the CPU oracle = restatement of
 ORC's Rust path, 1 core, on a bounded sample).
 """
 import argparse
@@ -239,6 +240,138 @@ def hardware_queue_note():
         return "KFD queue list not readable (%s)" % e.__class__.__name__
 
 
+DUMP_SAMPLE = 1 << 20  # cells per field that --dump-outputs writes, all ranks together (u, v, w, p and their indices: 40 MiB of float64)
+
+
+def dump_outputs(out_dir, solver, mesh, report, rank, world):
+    """--dump-outputs: what the last timed step computed, as a caller of Solver.iterate receives it — the fields u, v, w, p at a fixed
+    seeded sample of this rank's owned cells (all of them when there are fewer), the sample's cell indices and the step's report."""
+    n_own = int(getattr(mesh, "n_owned", mesh.n_cells))
+    k = DUMP_SAMPLE // world
+    idx = np.arange(n_own) if n_own <= k else np.sort(np.random.default_rng(0x4F5243).choice(n_own, k, replace=False))
+    arrays = dict(zip(("u", "v", "w", "p"), (f[idx] for f in solver.get_fields())))
+    arrays["cell_index"] = idx
+    arrays["report"] = report
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def full_measurements(args, solver, mesh, world, rank, mixed):
+    """--full: what the headline does not need, measured after the timed steps on every rank (the legs restore the snapshot and build
+    hierarchies of their own): the roofline legs of the dominant kernel and the per-level products of the Multigrid hierarchy."""
+    n_local = getattr(mesh, "n_owned", mesh.n_cells)  # rows of this rank's matrices
+    # dominant kernel: CSR(SELL-64) SpMV inside BiCGSTAB, timed live with HIP events on the library stream
+    solver.restore()  # the matrices of the timed iteration's state
+    solver.assemble_momentum_only()
+    spmv_ms, _ = solver.bench_spmv(args.spmv_reps)  # the plain product y = A x (no scalings, no epilogue): secondary figure
+    nnz_local = mesh.nnz
+    spmv_bytes = 12.0 * nnz_local + 20.0 * n_local  # SURVEY §8d: f64 value + i32 column per nnz; row_ptr, x, y per row
+    # the products INSIDE the BiCGSTAB loop, as the solver launches them on level 0 (two Jacobi scalings, reduction epilogues)
+    inloop = solver.bench_inloop_products(args.spmv_reps)
+    inloop_ms = 0.5 * (inloop[0] + inloop[1])  # one of each per BiCGSTAB iteration (linear_algebra.rs:256, :260)
+    achieved = spmv_bytes / (inloop_ms * 1e-3) / 1e9
+    triple_ms = 0.5 * (inloop[2] + inloop[3]) if inloop[2] > 0 else None
+    bicg_ms = solver.bench_bicgstab_iteration(10)
+    # per level of the momentum system's Multigrid hierarchy: rows, nnz, padded entries, product time, roofline fraction
+    levels = []
+    if args.solver in ("multigrid", "multigrid_gs") and world == 1:
+        solver.restore()
+        for lvl, (rows_l, nnz_l, padded_l, ms_l) in enumerate(solver.bench_amg_levels(20)):
+            # ALGORITHMIC bytes per product (SURVEY 8d): value + 4-byte column per stored entry, row length + x + y per row.  Every level's
+            # smoothing solve materialises its Jacobi-scaled values (orc_bench_amg_levels does the same), so no product reads a scaling
+            # vector (ADVICE r03: r03 added 8 n on levels 2-3 by mistake); the launches really stream 2-byte columns / window positions,
+            # so `frac_of_peak` is algorithmic throughput, not traffic — profiles/r04_pmc_products.csv has the measured bytes per level.
+            bytes_l = 12.0 * nnz_l + 20.0 * rows_l
+            levels.append({"level": lvl, "rows": rows_l, "nnz": nnz_l, "padded": padded_l, "us_per_product": ms_l * 1e3,
+                           "algorithmic_bytes": bytes_l, "GBs": bytes_l / (ms_l * 1e-3) / 1e9,
+                           "frac_of_peak": bytes_l / (ms_l * 1e-3) / 1e9 / HBM_PEAK_GBS})
+        if args.levels_csv and rank == 0:
+            with open(args.levels_csv, "w") as fh:
+                fh.write("level,rows,nnz,padded_entries,padding_ratio,us_per_product,algorithmic_bytes_12nnz_20n,algorithmic_GB_per_s,algorithmic_frac_of_8TBs\n")
+                for L in levels:
+                    fh.write("%d,%d,%d,%d,%.4f,%.2f,%.0f,%.1f,%.4f\n" % (L["level"], L["rows"], L["nnz"], L["padded"], L["padded"] / max(L["nnz"], 1),
+                                                                        L["us_per_product"], L["algorithmic_bytes"], L["GBs"], L["frac_of_peak"]))
+    gs = None
+    if args.solver in ("bicgstab_gs", "multigrid_gs") and world == 1:
+        # BASELINE configs[2]: the time-dominant kernel is the multicolour Gauss-Seidel sweep (preconditioner application): one sweep =
+        # n_colors launches of gs_color_sorted_k and moves one SpMV's bytes + the right-hand side (SURVEY K6)
+        gs_ms, gs_colors = solver.bench_gs_sweep(args.spmv_reps)
+        gs_bytes = spmv_bytes + 8.0 * n_local
+        ms1, ms3, _ = solver.bench_gs_sweep0(args.spmv_reps)  # [r04] what the slot-space solver launches: from zero, no fill, u/v/w per launch
+        gs = {"kernel": "gsx_sweep0_k<3> (u, v, w per colour launch; gsx_sweep0_k<1> for the p' system)", "launches_per_sweep": gs_colors,
+              "three_systems": {"avg_sweep_ms": ms3, "algorithmic_bytes_per_sweep": 3.0 * gs_bytes, "achieved": 3.0 * gs_bytes / (ms3 * 1e-3) / 1e9,
+                                "frac": 3.0 * gs_bytes / (ms3 * 1e-3) / 1e9 / HBM_PEAK_GBS},
+              "one_system": {"avg_sweep_ms": ms1, "algorithmic_bytes_per_sweep": gs_bytes, "achieved": gs_bytes / (ms1 * 1e-3) / 1e9,
+                             "frac": gs_bytes / (ms1 * 1e-3) / 1e9 / HBM_PEAK_GBS},
+              "r03_kernel_gs_color_sorted_k": {"avg_sweep_ms": gs_ms, "frac": gs_bytes / (gs_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
+              "avg_sweep_ms": ms3, "avg_launch_ms": ms3 / max(gs_colors, 1),
+              "algorithmic_bytes_per_sweep": 3.0 * gs_bytes, "achieved": 3.0 * gs_bytes / (ms3 * 1e-3) / 1e9, "frac": 3.0 * gs_bytes / (ms3 * 1e-3) / 1e9 / HBM_PEAK_GBS,
+              "note": "one sweep = 12 nnz + 20 n (SURVEY 8d) + 8 n (the right-hand side); at ~1 M cells the matrix (62 MB) lives in the 256 MiB "
+                      "Infinity Cache and a launch covers 1/n_colors of the rows: these launches are latency-, not HBM-bound"}
+    if gs is not None and args.solver == "multigrid_gs":
+        # the smoother's sweeps start from the current iterate, not from zero: gs_color_sorted_k on every level is what this solver launches
+        gs.update({"kernel": "gs_color_sorted_k (level 0: the smoother's general sweep; gsx_sweep0_k belongs to the bicgstab_gs solver)",
+                   "avg_sweep_ms": gs_ms, "avg_launch_ms": gs_ms / max(gs_colors, 1), "algorithmic_bytes_per_sweep": gs_bytes,
+                   "achieved": gs_bytes / (gs_ms * 1e-3) / 1e9, "frac": gs_bytes / (gs_ms * 1e-3) / 1e9 / HBM_PEAK_GBS})
+    bicg_bytes = 2.0 * spmv_bytes + 104.0 * n_local
+    # Memory-side traffic per launch from the PMC counters (TCC_EA0_RDREQ by request size + TCC_EA0_WRREQ, separate rocprofv3
+    # --pmc passes: scripts/gpu_pmc.sh; equal to FETCH_SIZE x 2 + WRITE_SIZE of MI355X_MICROARCH.md §HBM for this
+    # kernel): bench.py cannot collect counters itself, so it quotes the committed profile of the same kernel on the same
+    # matrix when one exists, else null.
+    variant = getattr(solver, "inloop_variant", "false, true, false")  # "<narrow columns>, <scaled on the fly>, <non-temporal matrix loads>" as launched
+    KERNEL = "spmv_uniform_k<EpiStoreSum, false, true, %s> / <EpiTs, false, true, %s>" % (variant, variant)
+    traffic, traffic_source = None, None
+    try:
+        pmc_file = PMC_FILE_CONFIG5 if mixed else PMC_FILE
+        pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_file)))
+        # the counters must be those of THIS kernel on THIS matrix: anything else is not quoted
+        if pmc["n"] == n_local and pmc["nnz"] == nnz_local and pmc["kernel"] == KERNEL:
+            traffic = pmc["hbm_bytes_per_launch"]
+            traffic_source = "profiles/%s (%s)" % (pmc_file, pmc.get("method", "rocprofv3 --pmc"))
+    except Exception:
+        traffic = None
+    return {
+        "roofline": {
+            "kernel": KERNEL,
+            "kernel_role": "SELL-64 CSR SpMV INSIDE the BiCGSTAB loop on level 0 (a_u of the momentum system, values scaled by the arm's Jacobi "
+                           "preconditioner and the smoother's nested one — materialised once per smoothing solve — with the reduction epilogues: "
+                           "nu = A p + sum(nu), t = A s + t.s, t.t), one system per launch — what the p' solve and every one-system solve launch; "
+                           "HIP events on the library stream around %d launches each" % args.spmv_reps,
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic,
+            "traffic_source": traffic_source,
+            "avg_launch_ms": inloop_ms,
+            "avg_launch_ms_by_epilogue": {"EpiStoreSum": inloop[0], "EpiTs": inloop[1]},
+            "algorithmic_bytes_per_launch": spmv_bytes,
+            "algorithmic_bytes_definition": "SURVEY 8(d): 12 nnz + 20 n per system (f64 value + i32 column per entry; row length, x, y per row); the "
+                                            "epilogue's operand (8 n, EpiTs) the in-loop kernel also reads is NOT counted; with the narrow column image "
+                                            "(template argument 4 = true) the launch streams 2-byte columns, so `frac` is algorithmic throughput",
+            "three_systems_per_launch": None if triple_ms is None else {
+                "kernel": "spmv3_uniform_k<EpiStoreSum3, 4, true, %s> / <EpiTs3, 4, true, %s>" % (variant, variant),
+                "avg_launch_ms": triple_ms,
+                "avg_launch_ms_by_epilogue": {"EpiStoreSum3": inloop[2], "EpiTs3": inloop[3]},
+                "algorithmic_bytes_per_launch": 3.0 * spmv_bytes,
+                "achieved": 3.0 * spmv_bytes / (triple_ms * 1e-3) / 1e9,
+                "frac": 3.0 * spmv_bytes / (triple_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "note": "u, v, w momentum products in one launch: 3 SpMV units of SURVEY 8(d); the launch itself moves 28 nnz + 60 n bytes (one "
+                        "column stream for three value streams), so `frac` is algorithmic throughput, not traffic",
+            },
+            "plain_product": {"kernel": "spmv_uniform_k<EpiStore, false, true, %s, false>" % variant.split(",")[0], "avg_launch_ms": spmv_ms,
+                              "frac": spmv_bytes / (spmv_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
+            "bicgstab_iteration_ms": bicg_ms,
+            "bicgstab_iteration_GBs": bicg_bytes / (bicg_ms * 1e-3) / 1e9,
+            "gauss_seidel_sweep": gs,
+        },
+        "amg_levels": levels
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -258,14 +391,23 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="N > 1: weak (default, what the driver's scaling run times) = every rank owns "
                     "an nx x ny x nz slab of an N times deeper channel; strong = the SAME nx x ny x nz mesh cut into N z-slabs (BASELINE configs[3]'s "
                     "'1 and 2x MI355X' on one ~10 M-cell mesh)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--spmv-reps", type=int, default=50)
-    ap.add_argument("--levels-csv", default=None, help="write the per-level product table (profiles/rNN_levels.csv)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure what the headline does not need: the roofline "
+                    "legs (in-loop products, plain product, BiCGSTAB iteration, Gauss-Seidel sweeps), the per-level products of the Multigrid "
+                    "hierarchy and the CPU oracle's baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the fields the last timed step computed to DIR/<name>.npy "
+                    "(float64): u, v, w, p at a fixed seeded sample of the owned cells (cell_index: which ones), and the step's report")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle's baseline")
+    ap.add_argument("--spmv-reps", type=int, default=50, help="--full: launches per product measurement")
+    ap.add_argument("--levels-csv", default=None, help="--full: write the per-level product table (profiles/rNN_levels.csv)")
     ap.add_argument("--spin-up", type=int, default=2, help="untimed SIMPLE iterations before the snapshot every timed step restores "
                     "(the timed iteration is number spin-up + 1 of the run; its cost grows slowly with the state)")
     ap.add_argument("--dry-run", action="store_true", help="launcher rehearsal (CPU test of `--gpus N` without a launcher): the ranks join the "
                     "gloo control plane, agree on a number and rank 0 prints a line with value null; no GPU work")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.levels_csv and not args.full:
+        ap.error("--levels-csv needs --full (the per-level products are measured there)")
     dflt = (400, 160, 160) if args.workload == "hex" else (252, 100, 72)
     args.nx, args.ny, args.nz = (v if v is not None else d for v, d in zip((args.nx, args.ny, args.nz), dflt))
 
@@ -288,6 +430,9 @@ def main():
         import torch
         import torch.distributed as dist
         dist.init_process_group(backend="gloo")  # control plane only; the data path uses RCCL inside liborc_amd
+        # the ranks leave this rendezvous together: from here their watchdogs run in step (armed at 'start', they were as far apart as
+        # the ranks' start-up, and the first rank to report could end the group before the others had said anything)
+        wd.kick("control plane")
     if args.dry_run:
         time.sleep(float(os.environ.get("ORC_BENCH_DRY_RUN_SLEEP", "0")))  # (tests: a rank that hangs — for the watchdog and for the launcher's clean-up)
         seen = world
@@ -455,61 +600,11 @@ def main():
     free_b, total_b = ctypes.c_int64(0), ctypes.c_int64(0)
     orc_amd._lib.check(orc_amd._lib.lib().orc_device_memory(ctypes.byref(free_b), ctypes.byref(total_b)))
     hbm_used_gb = (total_b.value - free_b.value) / 1e9
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, mesh, last_rep, rank, world)
 
-    # dominant kernel: CSR(SELL-64) SpMV inside BiCGSTAB, timed live with HIP events on the library stream
-    solver.restore()  # the matrices of the timed iteration's state
-    solver.assemble_momentum_only()
-    spmv_ms, _ = solver.bench_spmv(args.spmv_reps)  # the plain product y = A x (no scalings, no epilogue): secondary figure
-    n_local = getattr(mesh, "n_owned", mesh.n_cells)  # rows of this rank's matrices
-    nnz_local = mesh.nnz
-    spmv_bytes = 12.0 * nnz_local + 20.0 * n_local  # f64 value + i32 column per nnz; row_ptr, x, y per row
-    # the products INSIDE the BiCGSTAB loop, as the solver launches them on level 0 (two Jacobi scalings, reduction epilogues)
-    inloop = solver.bench_inloop_products(args.spmv_reps)
-    inloop_ms = 0.5 * (inloop[0] + inloop[1])  # one of each per BiCGSTAB iteration (linear_algebra.rs:256, :260)
-    achieved = spmv_bytes / (inloop_ms * 1e-3) / 1e9
-    triple_ms = 0.5 * (inloop[2] + inloop[3]) if inloop[2] > 0 else None
-    bicg_ms = solver.bench_bicgstab_iteration(10)
-    # per level of the momentum system's Multigrid hierarchy: rows, nnz, padded entries, product time, roofline fraction
-    levels = []
-    if args.solver in ("multigrid", "multigrid_gs") and world == 1:
-        solver.restore()
-        for lvl, (rows_l, nnz_l, padded_l, ms_l) in enumerate(solver.bench_amg_levels(20)):
-            # ALGORITHMIC bytes per product: value + 4-byte column per stored entry, row length + x + y per row.  Every level's
-            # smoothing solve materialises its Jacobi-scaled values (orc_bench_amg_levels does the same), so no product reads a scaling
-            # vector (r03 added 8 n on levels 2-3 by mistake); the launches really stream 2-byte columns / window positions,
-            # so `frac_of_peak` is algorithmic throughput, not traffic — profiles/r04_pmc_products.csv has the measured bytes per level.
-            bytes_l = 12.0 * nnz_l + 20.0 * rows_l
-            levels.append({"level": lvl, "rows": rows_l, "nnz": nnz_l, "padded": padded_l, "us_per_product": ms_l * 1e3,
-                           "algorithmic_bytes": bytes_l, "GBs": bytes_l / (ms_l * 1e-3) / 1e9,
-                           "frac_of_peak": bytes_l / (ms_l * 1e-3) / 1e9 / HBM_PEAK_GBS})
-        if args.levels_csv and rank == 0:
-            with open(args.levels_csv, "w") as fh:
-                fh.write("level,rows,nnz,padded_entries,padding_ratio,us_per_product,algorithmic_bytes_12nnz_20n,algorithmic_GB_per_s,algorithmic_frac_of_8TBs\n")
-                for L in levels:
-                    fh.write("%d,%d,%d,%d,%.4f,%.2f,%.0f,%.1f,%.4f\n" % (L["level"], L["rows"], L["nnz"], L["padded"], L["padded"] / max(L["nnz"], 1),
-                                                                        L["us_per_product"], L["algorithmic_bytes"], L["GBs"], L["frac_of_peak"]))
-    gs = None
-    if args.solver in ("bicgstab_gs", "multigrid_gs") and world == 1:
-        # BASELINE configs[2]: the time-dominant kernel is the multicolour Gauss-Seidel sweep (preconditioner application): one sweep =
-        # n_colors launches of gs_color_sorted_k and moves one SpMV's bytes + the right-hand side
-        gs_ms, gs_colors = solver.bench_gs_sweep(args.spmv_reps)
-        gs_bytes = spmv_bytes + 8.0 * n_local
-        ms1, ms3, _ = solver.bench_gs_sweep0(args.spmv_reps)  # [r04] what the slot-space solver launches: from zero, no fill, u/v/w per launch
-        gs = {"kernel": "gsx_sweep0_k<3> (u, v, w per colour launch; gsx_sweep0_k<1> for the p' system)", "launches_per_sweep": gs_colors,
-              "three_systems": {"avg_sweep_ms": ms3, "algorithmic_bytes_per_sweep": 3.0 * gs_bytes, "achieved": 3.0 * gs_bytes / (ms3 * 1e-3) / 1e9,
-                                "frac": 3.0 * gs_bytes / (ms3 * 1e-3) / 1e9 / HBM_PEAK_GBS},
-              "one_system": {"avg_sweep_ms": ms1, "algorithmic_bytes_per_sweep": gs_bytes, "achieved": gs_bytes / (ms1 * 1e-3) / 1e9,
-                             "frac": gs_bytes / (ms1 * 1e-3) / 1e9 / HBM_PEAK_GBS},
-              "r03_kernel_gs_color_sorted_k": {"avg_sweep_ms": gs_ms, "frac": gs_bytes / (gs_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-              "avg_sweep_ms": ms3, "avg_launch_ms": ms3 / max(gs_colors, 1),
-              "algorithmic_bytes_per_sweep": 3.0 * gs_bytes, "achieved": 3.0 * gs_bytes / (ms3 * 1e-3) / 1e9, "frac": 3.0 * gs_bytes / (ms3 * 1e-3) / 1e9 / HBM_PEAK_GBS,
-              "note": "one sweep = 12 nnz + 20 n (SURVEY 8d) + 8 n (the right-hand side); at ~1 M cells the matrix (62 MB) lives in the 256 MiB "
-                      "Infinity Cache and a launch covers 1/n_colors of the rows: these launches are latency-, not HBM-bound"}
-    if gs is not None and args.solver == "multigrid_gs":
-        # the smoother's sweeps start from the current iterate, not from zero: gs_color_sorted_k on every level is what this solver launches
-        gs.update({"kernel": "gs_color_sorted_k (level 0: the smoother's general sweep; gsx_sweep0_k belongs to the bicgstab_gs solver)",
-                   "avg_sweep_ms": gs_ms, "avg_launch_ms": gs_ms / max(gs_colors, 1), "algorithmic_bytes_per_sweep": gs_bytes,
-                   "achieved": gs_bytes / (gs_ms * 1e-3) / 1e9, "frac": gs_bytes / (gs_ms * 1e-3) / 1e9 / HBM_PEAK_GBS})
+    full = full_measurements(args, solver, mesh, world, rank, args.workload == "config5") if args.full else None  # every rank
+
     nz_total = args.nz if strong else nz * world  # layers of the whole mesh
     key = (args.nx, args.ny, args.nz, args.momentum, args.solver)
     workload_name = ("BASELINE configs[3]" if key == (400, 160, 160, "umist", "multigrid")
@@ -520,24 +615,6 @@ def main():
         workload_name = "BASELINE configs[4]" if (key[:3] == (252, 100, 72) and args.solver == "multigrid") else "custom (BASELINE configs[4] family)"
     if strong:
         workload_name += " on %dx MI355X (strong scaling: ONE %dx%dx%d mesh cut into %d z-slabs)" % (world, nx, ny, nz_total, world)
-    bicg_bytes = 2.0 * spmv_bytes + 104.0 * n_local
-    # Memory-side traffic per launch from the PMC counters (TCC_EA0_RDREQ by request size + TCC_EA0_WRREQ, separate rocprofv3
-    # --pmc passes: scripts/gpu_pmc.sh; equal to FETCH_SIZE x 2 + WRITE_SIZE of MI355X_MICROARCH.md §HBM for this
-    # kernel): bench.py cannot collect counters itself, so it quotes the committed profile of the same kernel on the same
-    # matrix when one exists, else null.
-    variant = getattr(solver, "inloop_variant", "false, true, false")  # "<narrow columns>, <scaled on the fly>, <non-temporal matrix loads>" as launched
-    KERNEL = "spmv_uniform_k<EpiStoreSum, false, true, %s> / <EpiTs, false, true, %s>" % (variant, variant)
-    traffic, traffic_source = None, None
-    try:
-        pmc_file = PMC_FILE_CONFIG5 if mixed else PMC_FILE
-        pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_file)))
-        # the counters must be those of THIS kernel on THIS matrix: anything else is not quoted
-        if pmc["n"] == n_local and pmc["nnz"] == nnz_local and pmc["kernel"] == KERNEL:
-            traffic = pmc["hbm_bytes_per_launch"]
-            traffic_source = "profiles/%s (%s)" % (pmc_file, pmc.get("method", "rocprofv3 --pmc"))
-    except Exception:
-        traffic = None
-
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         units = n_cells_total / float(REF_CELLS)  # 10.24M-cell SIMPLE iterations per step (N at weak scaling)
@@ -585,42 +662,6 @@ def main():
                 "setup_s": round(t_setup, 2),
                 "hbm_used_gb": round(hbm_used_gb, 1),
             },
-            "roofline": {
-                "kernel": KERNEL,
-                "kernel_role": "SELL-64 CSR SpMV INSIDE the BiCGSTAB loop on level 0 (a_u of the momentum system, values scaled by the arm's Jacobi "
-                               "preconditioner and the smoother's nested one — materialised once per smoothing solve — with the reduction epilogues: "
-                               "nu = A p + sum(nu), t = A s + t.s, t.t), one system per launch — what the p' solve and every one-system solve launch; "
-                               "HIP events on the library stream around %d launches each" % args.spmv_reps,
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_source": traffic_source,
-                "avg_launch_ms": inloop_ms,
-                "avg_launch_ms_by_epilogue": {"EpiStoreSum": inloop[0], "EpiTs": inloop[1]},
-                "algorithmic_bytes_per_launch": spmv_bytes,
-                "algorithmic_bytes_definition": "SURVEY 8(d): 12 nnz + 20 n per system (f64 value + i32 column per entry; row length, x, y per row); the "
-                                                "epilogue's operand (8 n, EpiTs) the in-loop kernel also reads is NOT counted; with the narrow column image "
-                                                "(template argument 4 = true) the launch streams 2-byte columns, so `frac` is algorithmic throughput",
-                "three_systems_per_launch": None if triple_ms is None else {
-                    "kernel": "spmv3_uniform_k<EpiStoreSum3, 4, true, %s> / <EpiTs3, 4, true, %s>" % (variant, variant),
-                    "avg_launch_ms": triple_ms,
-                    "avg_launch_ms_by_epilogue": {"EpiStoreSum3": inloop[2], "EpiTs3": inloop[3]},
-                    "algorithmic_bytes_per_launch": 3.0 * spmv_bytes,
-                    "achieved": 3.0 * spmv_bytes / (triple_ms * 1e-3) / 1e9,
-                    "frac": 3.0 * spmv_bytes / (triple_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                    "note": "u, v, w momentum products in one launch: 3 SpMV units of SURVEY 8(d); the launch itself moves 28 nnz + 60 n bytes (one "
-                            "column stream for three value streams), so `frac` is algorithmic throughput, not traffic",
-                },
-                "plain_product": {"kernel": "spmv_uniform_k<EpiStore, false, true, %s, false>" % variant.split(",")[0], "avg_launch_ms": spmv_ms,
-                                  "frac": spmv_bytes / (spmv_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                "bicgstab_iteration_ms": bicg_ms,
-                "bicgstab_iteration_GBs": bicg_bytes / (bicg_ms * 1e-3) / 1e9,
-                "gauss_seidel_sweep": gs,
-            },
-            "amg_levels": levels,
             "multi_gpu": multi,
             "report_last": [float(x) for x in rep[-1]] if rep is not None and len(rep) else None,
             "report_trajectory": {"columns": ["u_mean", "v_mean", "w_mean", "velocity_correction_norm", "pressure_correction_norm"],
@@ -628,7 +669,9 @@ def main():
                                   "timed": [float(rep[-1][k]) for k in (0, 1, 2, 6, 7)] if rep is not None and len(rep) else None},
             "breakdown_guard_events_in_timed_region": int(guard_events_timed),
         }
-        if not args.no_cpu_baseline:
+        if full is not None:
+            out.update(full)
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(settings_kw, iters=3 if mixed else 6, mixed_ref_cells=(n_cells_total // world) if mixed else None)
         print(json.dumps(out), flush=True)
     wd.stop()

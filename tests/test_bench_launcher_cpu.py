@@ -100,7 +100,7 @@ def test_a_stuck_rank_reports_and_exits_nonzero():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0
     # (the two ranks write to one pipe: their lines may interleave, so count the pieces rather than match whole lines)
-    assert r.stderr.count("no progress for 3 s after 'start'") == 2 and "[bench watchdog r" in r.stderr, r.stderr[-3000:]
+    assert r.stderr.count("no progress for 3 s after 'control plane'") == 2 and "[bench watchdog r" in r.stderr, r.stderr[-3000:]
     assert "most recent call first" in r.stderr  # the stacks
 
 
@@ -128,3 +128,11 @@ def test_strong_scaling_cut_is_the_one_mesh():
         for x, y in zip(bench.initial_fields(np.asarray(a["cell_centroid"]), ids=gids), f_whole):  # (what make_slab_solver(global_noise=True) sets)
             assert np.allclose(x, y[gids], rtol=1e-12, atol=0)
     assert np.array_equal(np.concatenate(seen), np.arange(whole.n_cells))
+
+
+@pytest.mark.parametrize("args, msg", [(["--steps", "0"], "--steps must be at least 1"), (["--levels-csv", "levels.csv"], "--levels-csv needs --full")])
+def test_bench_refuses_arguments_it_cannot_honour(args, msg, tmp_path):
+    """rejected while parsing, before anything touches a GPU: zero timed steps (ms_per_step would be undefined) and a per-level table without --full"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and msg in r.stderr, r.stderr[-2000:]
+    assert not os.listdir(str(tmp_path))

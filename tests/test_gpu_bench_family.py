@@ -265,3 +265,59 @@ def test_midsize_frozen_iteration_bit_exact_in_reference_order_and_product_defau
         assert err <= bar, "field %s: relative L2 over the samples %.3e, bar %.3e" % (name, err, bar)
     sens = g["association_sensitivity_report"]
     assert abs(rep[0][6] - ro[4]) <= 10 * sens[4] * ro[4] and abs(rep[0][7] - ro[5]) <= 10 * sens[5] * ro[5], (rep[0], ro)
+
+
+# ------------------------------------------------------------------ bench.py itself: what a plain run prints and dumps, and what --full adds
+def _bench(args, tmp_path):
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nx", "40", "--ny", "26", "--nz", "16", "--inner", "10"] + args,
+                       cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(gpu, tmp_path):
+    """`bench.py --dump-outputs DIR`: a plain run times exactly --steps steps, measures nothing beyond them, and writes the fields of its last
+    timed step — the same bits as the run it times (spin-up, snapshot, then restore + one SIMPLE iteration per warm-up and timed step) made here."""
+    import os
+    from orc_amd.mesh import Mesh, hex_channel, set_channel_bcs
+    from orc_amd.settings import MomentumDiscretization, NumericalSettings, SolutionMethod
+    from orc_amd.solver import Solver
+    out = _bench(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")], tmp_path)
+    assert out["status"] == 0 and out["steps"] == 3 and len(out["step_ms"]) == 3 and out["ms_per_step"] > 0
+    assert not {"roofline", "amg_levels", "cpu_baseline"} & set(out)
+    d = {n: np.load(str(tmp_path / "dump" / (n + ".npy"))) for n in ("u", "v", "w", "p", "cell_index", "report")}
+    assert sorted(os.listdir(str(tmp_path / "dump"))) == sorted(n + ".npy" for n in d)
+    assert all(x.dtype == np.float64 for x in d.values())
+    assert same_bits(d["report"], out["report_last"])
+    a = set_channel_bcs(hex_channel(40, 26, 16))
+    assert np.array_equal(d["cell_index"], np.arange(a.n_cells))  # fewer cells than the sample: all of them
+    kw = dict(momentum=MomentumDiscretization.TVD_UMIST, solver_type=SolutionMethod.Multigrid, iterations=10, momentum_relaxation=0.1,
+              pressure_relaxation=0.001)
+    s = Solver(Mesh(a), NumericalSettings.default(**kw), 1000.0, 1e-3)
+    s.set_fields(*bench.initial_fields(np.asarray(a["cell_centroid"])))
+    for _ in range(2):
+        assert s.iterate(1, report=True, raise_on_error=False)[0] == 0
+    s.snapshot()
+    for _ in range(1 + 3):
+        s.restore()
+        st, rep = s.iterate(1, report=True, raise_on_error=False)
+        assert st == 0
+    assert same_bits(d["report"], rep[0])
+    for name, x in zip("uvwp", s.get_fields()):
+        assert same_bits(d[name], x), name
+
+
+def test_bench_full_adds_the_measurement_legs(gpu, tmp_path):
+    """`bench.py --full`: the roofline legs and the per-level products of the Multigrid hierarchy (here without the CPU oracle's baseline)."""
+    out = _bench(["--full", "--steps", "1", "--warmup", "0", "--spmv-reps", "2", "--no-cpu-baseline", "--levels-csv", str(tmp_path / "levels.csv")], tmp_path)
+    assert out["status"] == 0 and out["steps"] == 1 and "cpu_baseline" not in out
+    assert out["roofline"]["avg_launch_ms"] > 0 and out["roofline"]["bicgstab_iteration_ms"] > 0
+    assert len(out["amg_levels"]) >= 1 and all(L["us_per_product"] > 0 for L in out["amg_levels"])
+    assert len(open(str(tmp_path / "levels.csv")).read().splitlines()) == 1 + len(out["amg_levels"])
