@@ -197,6 +197,27 @@ int64_t orc_breakdown_guard_events(int reset);
 int orc_set_reduction_order(int order);
 /* sweeps the Jacobi arm executed in the last orc_iterative_solve (linear_algebra.rs:188-217) */
 int64_t orc_last_jacobi_sweeps(void);
+/* ORC_SOLVER_GMRES (extension, no reference counterpart; ORC's own TODO at lib.rs:170): restarted GMRES(m).
+ *  - preconditioner: ORC_PRECOND_JACOBI is the left scaling p_inv * a, p_inv * b of every arm (linear_algebra.rs:159-167);
+ *    every residual below is one of that system.  relaxation_factor is ignored, and so is reduction_order: there is no
+ *    reference arithmetic to match, the sums are always per-workgroup trees folded in a fixed order.
+ *  - iteration_count = Arnoldi steps (products with A) over all restarts; m = min(restart, iteration_count);
+ *    iteration_count == 0 or n == 0 leaves x unchanged.
+ *  - a cycle: r = b - A x, beta = |r| (beta0: of the first cycle), v0 = r / beta, g = (beta, 0, ...); step j: w = A v_j,
+ *    classical Gram-Schmidt twice (h1 = V^T w; w -= V h1; h2 = V^T w; w -= V h2; h = h1 + h2), h_{j+1,j} = |w|,
+ *    v_{j+1} = w / h_{j+1,j}; the earlier Givens rotations on column j, the new one from hypot, g updated; at the end of
+ *    the cycle R y = g by back substitution and x += V y.
+ *  - the cycle and the solve end early when |g_{j+1}| <= convergence_threshold * beta0 (never with a threshold <= 0), on a
+ *    happy breakdown h_{j+1,j} <= 1e-14 * |h_{:,j}| (x takes the update with that column), or when the steps are spent.
+ *    A new cycle whose beta is 0 stops without touching x.
+ *  - a non-finite beta0 or Hessenberg entry: with breakdown_guard on, x keeps the value of the last completed cycle, the
+ *    solve stops and orc_breakdown_guard_events counts one event; with it off the update is applied and NaN propagates.
+ *  - bit-reproducible from run to run on one device (no float atomics); no host synchronisation inside the solve.
+ * Process-wide default of OrcSettings.gmres_restart for orc_iterative_solve: 0 = 30, 1..64; anything else makes the GMRES
+ * arm return ORC_ERR_BAD_ARGUMENT. */
+int orc_set_gmres_restart(int m);
+/* the last orc_iterative_solve's GMRES arm: Arnoldi steps, cycles, beta0 and the final residual estimate |g| */
+int orc_last_gmres_stats(int64_t *steps, int64_t *cycles, double *initial_residual, double *final_estimate);
 /* y = A x: the `&CsrMatrix * &DVector` product the reference takes from nalgebra-sparse
  * (linear_algebra.rs:256,260); row sums accumulate in ascending-column order from 0.0, so y is
  * bit-identical to the CPU product.  `reps` > 1 repeats the launch (timing); avg_ms may be NULL. */

@@ -64,7 +64,8 @@ enum OrcSolutionMethod {
     /* --- new-build extensions, no reference counterpart --- */
     ORC_SOLVER_MULTICOLOR_GS = 16,         /* multicolour Gauss-Seidel sweeps */
     ORC_SOLVER_BICGSTAB_GS_PRECOND = 17,   /* right-preconditioned BiCGSTAB, M = one multicolour GS sweep */
-    ORC_SOLVER_MULTIGRID_GS = 18           /* Multigrid arm with multicolour GS as the smoother */
+    ORC_SOLVER_MULTIGRID_GS = 18,          /* Multigrid arm with multicolour GS as the smoother */
+    ORC_SOLVER_GMRES = 19                  /* restarted GMRES(m), CGS2 Arnoldi, relative stopping test (orc_amd.h: orc_set_gmres_restart) */
 };
 
 /* settings::PreconditionMethod (lib.rs:181-185) */
@@ -148,7 +149,8 @@ typedef struct OrcSettings {
                                         "solution diverged".  0 = reference behaviour (NaN propagates).  Every solve in
                                         which the guard fired is counted: orc_breakdown_guard_events(). */
     int32_t reduction_order;         /* OrcReductionOrder; default TREE */
-    int32_t reserved0;
+    int32_t gmres_restart;           /* new-build extension: restart length m of ORC_SOLVER_GMRES; 0 (default) = 30, 1..64 accepted,
+                                        anything else is ORC_ERR_BAD_ARGUMENT when the GMRES arm runs */
 } OrcSettings;
 
 #ifdef __cplusplus

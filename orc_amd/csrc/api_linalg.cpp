@@ -227,4 +227,18 @@ int orc_debug_coloring(int64_t n, const int64_t *row_ptr, const int64_t *col_idx
 
 int64_t orc_last_jacobi_sweeps(void) { return orc::g_last_stats.jacobi_sweeps; }
 
+int orc_set_gmres_restart(int m) {
+    orc::ctx().gmres_restart = m;  // checked (1..64, 0 = default) when the GMRES arm runs
+    return ORC_OK;
+}
+
+int orc_last_gmres_stats(int64_t *steps, int64_t *cycles, double *initial_residual, double *final_estimate) {
+    const orc::SolveStats &s = orc::g_last_stats;
+    if (steps) *steps = s.gmres_steps;
+    if (cycles) *cycles = s.gmres_cycles;
+    if (initial_residual) *initial_residual = s.gmres_beta0;
+    if (final_estimate) *final_estimate = s.gmres_estimate;
+    return ORC_OK;
+}
+
 }  // extern "C"

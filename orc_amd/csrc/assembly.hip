@@ -1150,9 +1150,10 @@ static int solve_field_on(SolverState &s, DevBuf<double> &a, DevBuf<double> &b, 
     const OrcSettings &t = s.settings;
     if (arena.empty()) ORC_TRY(arena.reset());  // nothing of the previous solve is alive: a fragmented reservation is folded into one chunk
     if (side_arena && side_arena->empty()) ORC_TRY(side_arena->reset());
-    CtxDefaultsScope restore_defaults(ctx());  // this solver's guard and reduction order for the solve only
+    CtxDefaultsScope restore_defaults(ctx());  // this solver's guard, reduction order and GMRES restart for the solve only
     ctx().breakdown_guard = t.breakdown_guard != 0;
     ctx().reduction_order = t.reduction_order;
+    ctx().gmres_restart = t.gmres_restart;
     stats.side = nullptr;
     // the momentum systems share their pairing's starting state (the caller has opened the exchange: SiblingPairing::begin)
     stats.sibling = (s.sibling_pairing && eq < 3) ? &s.sibling : nullptr;

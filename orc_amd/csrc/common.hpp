@@ -29,6 +29,7 @@ struct Ctx {
     bool profile = false;
     bool breakdown_guard = true;  // OrcSettings.breakdown_guard of the running solve
     int reduction_order = 0;      // OrcReductionOrder of the running solve: 0 = wave trees, 1 = the reference's (nalgebra) association
+    int gmres_restart = 0;        // OrcSettings.gmres_restart of the running solve (0 = the default length)
     long long halo_overlaps = 0;  // level-0 products that ran beside their halo exchange (orc_debug_halo_overlaps)
     int *guard_events = nullptr;  // device counter: BiCGSTAB solves in which the breakdown guard fired (orc_breakdown_guard_events)
     // multi-GPU (comm.cpp)
@@ -43,14 +44,15 @@ struct CtxScope {
     ~CtxScope();
 };
 
-// A solver runs its solves with ITS guard and reduction order; the process-wide defaults (orc_set_breakdown_guard,
-// orc_set_reduction_order: what orc_iterative_solve uses) come back on every exit.
+// A solver runs its solves with ITS guard, reduction order and GMRES restart length; the process-wide defaults
+// (orc_set_breakdown_guard, orc_set_reduction_order, orc_set_gmres_restart: what orc_iterative_solve uses) come back on every exit.
 struct CtxDefaultsScope {
     Ctx &c;
     bool guard;
     int order;
-    explicit CtxDefaultsScope(Ctx &cc) : c(cc), guard(cc.breakdown_guard), order(cc.reduction_order) {}
-    ~CtxDefaultsScope() { c.breakdown_guard = guard; c.reduction_order = order; }
+    int restart;
+    explicit CtxDefaultsScope(Ctx &cc) : c(cc), guard(cc.breakdown_guard), order(cc.reduction_order), restart(cc.gmres_restart) {}
+    ~CtxDefaultsScope() { c.breakdown_guard = guard; c.reduction_order = order; c.gmres_restart = restart; }
     CtxDefaultsScope(const CtxDefaultsScope &) = delete;
     CtxDefaultsScope &operator=(const CtxDefaultsScope &) = delete;
 };

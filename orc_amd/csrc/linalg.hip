@@ -525,6 +525,14 @@ int spmv_dev(const MatView &A, const double *x, double *y) {
     return launch_spmv(A, x, e, nullptr, nullptr);
 }
 
+// the GMRES arm's products (gmres.hip): y = A x, and r = b - A x with the partial sums of |r|^2, both no-ops under skip_flags
+int gmres_product_dev(const MatView &A, const double *x, double *y, const double *skip_flags) {
+    return launch_spmv(A, x, EpiStore{y}, nullptr, nullptr, skip_flags);
+}
+int gmres_residual_dev(const MatView &A, const double *b, const double *x, double *r, double *partials, int *grid, const double *skip_flags) {
+    return launch_spmv(A, x, EpiResidualNorm{b, r}, partials, grid, skip_flags);
+}
+
 int residual_dev(const MatView &A, const double *b, const double *x, double *r) {
     int g = 0;
     static double *const dummy = [] {  // thread-safe one-time allocation (concurrent solves)
@@ -1674,6 +1682,8 @@ int multigrid_arm_dev(const MatView &A, const double *b, double *x, uint64_t ite
                       double convergence_threshold, int preconditioner, Arena &arena, SolveStats *stats, int smoother);  // amg.hip
 int gs_arm_dev(const MatView &A, const double *b, double *x, uint64_t iteration_count, double relaxation_factor, int method,
                Arena &arena);  // gs.hip (extension)
+int gmres_dev(const MatView &A, const double *b, double *x, uint64_t iteration_count, double convergence_threshold, Arena &arena,
+              SolveStats *stats);  // gmres.hip (extension)
 
 static int iterative_solve_body(const MatView &A_in, const double *b_in, double *x, uint64_t iteration_count, int method,
                                 double relaxation_factor, double convergence_threshold, int preconditioner, Arena &arena,
@@ -1718,6 +1728,9 @@ static int iterative_solve_body(const MatView &A_in, const double *b_in, double 
     case ORC_SOLVER_MULTICOLOR_GS:
     case ORC_SOLVER_BICGSTAB_GS_PRECOND:
         st = gs_arm_dev(A, b, x, iteration_count, relaxation_factor, method, arena);
+        break;
+    case ORC_SOLVER_GMRES:  // extension: relaxation_factor and reduction_order play no part (tree sums always)
+        st = gmres_dev(A, b, x, iteration_count, convergence_threshold, arena, stats);
         break;
     case ORC_SOLVER_GAUSS_SEIDEL:
         // The reference's arm scans every (i, j) through get(), which panics on the first

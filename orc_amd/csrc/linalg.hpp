@@ -237,6 +237,8 @@ struct SolveStats {
     SolveSide *side = nullptr;  // optional, owned by the caller
     const AmgHierarchy *hierarchy = nullptr;  // optional: a hierarchy prepared for exactly this matrix
     int64_t jacobi_sweeps = 0;
+    int64_t gmres_steps = 0, gmres_cycles = 0;  // GMRES arm: Arnoldi steps and cycles run, beta_0 and the final |g| estimate
+    double gmres_beta0 = 0., gmres_estimate = 0.;
     int amg_levels = 0;
     int64_t amg_rows[8] = {0};
     int64_t amg_nnz[8] = {0};

@@ -79,6 +79,20 @@ def last_jacobi_sweeps():
     return lib().orc_last_jacobi_sweeps()
 
 
+def set_gmres_restart(m):
+    """process-wide OrcSettings.gmres_restart for iterative_solve: 0 = the default (30), 1..64; anything else makes the GMRES
+    arm fail with ORC_ERR_BAD_ARGUMENT"""
+    check(lib().orc_set_gmres_restart(C.c_int(int(m))))
+
+
+def last_gmres_stats():
+    """(Arnoldi steps, cycles, beta0, final residual estimate |g|) of the last iterative_solve's GMRES arm"""
+    steps, cycles = C.c_int64(0), C.c_int64(0)
+    beta0, est = C.c_double(0.0), C.c_double(0.0)
+    check(lib().orc_last_gmres_stats(C.byref(steps), C.byref(cycles), C.byref(beta0), C.byref(est)))
+    return steps.value, cycles.value, beta0.value, est.value
+
+
 def csr_spmv(a, x, reps=1):
     """y = A x on the device; returns (y, avg_ms_per_launch)."""
     a = a.tocsr()
