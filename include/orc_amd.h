@@ -347,6 +347,12 @@ int orc_debug_stream_report(char *buf, int cap);
  * orc_amg_coarsen (same kernels), so a test can evaluate the same product on the oracle. */
 int orc_debug_amg_coarse_product(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, const double *values, int scaled, const double *x,
                                  double *y, int *has_window_mirror);
+/* orc_debug_amg_packed_mirror: the same set-up, and the coarse level's packed mirror and LDS x windows as the products read them:
+ * sizes = {coarse rows, slices, value slots, window-position slots, 256-row blocks} (0 slots: no mirror); the arrays (row_len [rows],
+ * pk_ptr [slices + 1], pk_col / pk_val [value slots], lptr [slices + 1], lidx [position slots], wcol [blocks * 5000], wsize [blocks])
+ * are written only if none of them is null, so a caller asks for the sizes first. */
+int orc_debug_amg_packed_mirror(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, const double *values, int64_t sizes[5], int32_t *row_len,
+                                int64_t *pk_ptr, int32_t *pk_col, double *pk_val, int64_t *lptr, uint16_t *lidx, int32_t *wcol, int32_t *wsize);
 /* collectives this process has issued since the last reset — halo exchanges (one grouped ncclSend/ncclRecv launch each) and
  * all-reduces, status agreements included: the latency-bound messages of a partitioned SIMPLE iteration */
 long long orc_debug_collectives(int reset);

@@ -642,27 +642,36 @@ __global__ __launch_bounds__(64) void galerkin_pack_fused_k(SellDev Pc, const lo
                 }
             }
             __syncthreads();
-            // ---- scatter: depth by depth, lane = row
+            // ---- scatter: depth by depth, lane = row.  The packed mirror goes by pairs of depths (PackedDev): a lane whose row is longer than
+            // the pair's first depth owns both slots, and a row of odd length fills its second one with padding (its own row as column, 0.0) —
+            // so the depths run on to the even end of the slice width.
             const int kend = min(kPackDepth, width - kc);
-            for (int q = 0; q < kend; ++q) {
+            const int kend_pk = pk_ptr ? min(kPackDepth, ((width + 1) & ~1) - kc) : kend;  // (kc and kPackDepth are even: no pair straddles two tiles)
+            int pair_rank = 0;
+            int64_t pair_base = 0;
+            for (int q = 0; q < kend_pk; ++q) {
                 const int k = kc + q;
                 const bool in = k < len;
                 const int c = (in && !kValuesOnly) ? t_col[q * 65 + lane] : (int)I;
                 const double v = in ? t_val[q * 65 + lane] : 0.;
-                const int64_t pos = base + (int64_t)k * 64 + lane;
-                if (live) {
+                if (live && q < kend) {
+                    const int64_t pos = base + (int64_t)k * 64 + lane;
                     if (!kValuesOnly) col_c[pos] = c;
                     val_c[pos] = v;
                     if (!kValuesOnly && in && c == (int)I) d = (int)pos;
                 }
                 if (pk_ptr) {
-                    const unsigned long long m = __ballot(in);
-                    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                    if (in) {
-                        if (!kValuesOnly) pk_col[pk_off + rank] = c;
-                        pk_val[pk_off + rank] = v;
+                    if ((k & 1) == 0) {  // wave-uniform
+                        const unsigned long long m = __ballot(in);
+                        pair_rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                        pair_base = pk_off;
+                        pk_off += 2 * (int64_t)__popcll(m);
                     }
-                    pk_off += __popcll(m);
+                    if ((k & ~1) < len) {
+                        const int64_t p = pair_base + 2 * pair_rank + (k & 1);
+                        if (!kValuesOnly) pk_col[p] = c;
+                        pk_val[p] = v;
+                    }
                 }
             }
             __syncthreads();
@@ -770,24 +779,32 @@ __device__ __forceinline__ long long block_excl_scan(long long v, long long *buf
     return r;
 }
 
-// slice widths -> slice_ptr and packed sizes -> pk_ptr.
-// One wavefront per slice reduces its 64 row lengths (SELL width * 64 and the packed size rounded up to 16 elements =
-// 128 bytes), then both tables are scanned (scan_excl_dev; a single workgroup reading all n row lengths itself took 0.9 + 1.4 ms
-// per level at 5 M rows).
+// slice widths -> slice_ptr and packed sizes -> pk_ptr (and the window positions' sizes -> XWinDev::lptr).
+// One wavefront per slice reduces its 64 row lengths (SELL width * 64; the packed slots: lengths rounded up to pairs, the slice to 16
+// elements = 128 bytes; the positions: lengths rounded up to chunks of 8, the slice to 64 = 128 bytes; the entries rounded up to 16, what
+// the launches decide by, PackedDev::total), then the tables are scanned (scan_excl_dev; a single workgroup reading all n row lengths
+// itself took 0.9 + 1.4 ms per level at 5 M rows).
 __global__ __launch_bounds__(kBlock) void slice_sizes_k(const int *__restrict__ row_len, int64_t n, int n_slices, int64_t *__restrict__ w_sell,
-                                                        int64_t *__restrict__ w_pk) {
+                                                        int64_t *__restrict__ w_pk, int64_t *__restrict__ w_pos, int64_t *__restrict__ w_tot) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t s = wave; s < n_slices; s += waves) {
         const int64_t r = s * 64 + lane;
         const int len = r < n ? row_len[r] : 0;
-        int mx = len, sum = len;
+        int mx = len, sum = len, pairs = (len + 1) >> 1, chunks = (len + kPackChunk - 1) / kPackChunk;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             mx = max(mx, __shfl_xor(mx, off, 64));
             sum += __shfl_xor(sum, off, 64);
+            pairs += __shfl_xor(pairs, off, 64);
+            chunks += __shfl_xor(chunks, off, 64);
         }
-        if (lane == 0) { w_sell[s] = (int64_t)mx * 64; w_pk[s] = ((int64_t)sum + 15) & ~(int64_t)15; }
+        if (lane == 0) {
+            w_sell[s] = (int64_t)mx * 64;
+            w_pk[s] = ((int64_t)pairs * 2 + 15) & ~(int64_t)15;
+            w_pos[s] = ((int64_t)chunks * kPackChunk + 63) & ~(int64_t)63;
+            w_tot[s] = ((int64_t)sum + 15) & ~(int64_t)15;
+        }
     }
 }
 // [r04] The same scans over the whole chip: one workgroup walking 80 000 slice totals took 0.1-0.2 ms (its threads' contiguous shares are
@@ -865,7 +882,7 @@ __device__ unsigned long long g_xwin_counters[3];
 // looks at those only.  (ORC_AMG_TRACE "[amg windows]": with 2 048 words half of the channel's level-2 / 3 blocks were left to the second pass.)
 constexpr int kXBitWordsSmall = 4096;
 template <int kWords, bool kSecond>
-__global__ __launch_bounds__(kBlock) void xwin_build_k(SellDev P, PackedDev pk, int *__restrict__ wcol, int *__restrict__ wsize,
+__global__ __launch_bounds__(kBlock) void xwin_build_k(SellDev P, const int64_t *__restrict__ lptr, int *__restrict__ wcol, int *__restrict__ wsize,
                                                        unsigned short *__restrict__ lidx, int64_t n_blocks, int win_cap, int bit_words, int pass_words,
                                                        int *__restrict__ pending /* blocks the first pass left to the second */) {
     if (kSecond && *pending == 0) return;
@@ -946,21 +963,30 @@ __global__ __launch_bounds__(kBlock) void xwin_build_k(SellDev P, PackedDev pk, 
         }
         if (tid == 0) wsize[b] = total;
         __syncthreads();
-        // window positions of the packed entries: wave per slice, depth by depth (the packed order of galerkin_pack_packed_k)
+        // window positions of the packed entries: wave per slice, chunk by chunk (XWinDev::lidx): 8 positions per lane whose row reaches the
+        // chunk, one 16-byte store; the positions past the row's end are 0
         const int64_t slice = b * 4 + wave;
         if (slice < P.n_slices) {
             const int64_t sbase = P.slice_ptr[slice];
             const int width = (int)((P.slice_ptr[slice + 1] - sbase) >> 6);
-            int64_t off = pk.ptr[slice];
-            for (int q = 0; q < width; ++q) {
-                const bool in = q < len;
+            int64_t off = lptr[slice];
+            for (int j0 = 0; j0 < width; j0 += kPackChunk) {
+                const bool in = j0 < len;
                 const unsigned long long m = __ballot(in);
                 const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
                 if (in) {
-                    const int c = P.col[sbase + (int64_t)q * 64 + lane] - cmin;
-                    lidx[off + rank] = (unsigned short)(wpre[c >> 5] + __popc(bits[c >> 5] & ((1u << (c & 31)) - 1u)));
+                    u32x4_t w = {0u, 0u, 0u, 0u};
+#pragma unroll
+                    for (int u = 0; u < kPackChunk; ++u) {
+                        if (j0 + u < len) {
+                            const int c = P.col[sbase + (int64_t)(j0 + u) * 64 + lane] - cmin;
+                            const unsigned pos = wpre[c >> 5] + __popc(bits[c >> 5] & ((1u << (c & 31)) - 1u));
+                            w[u >> 1] |= pos << (16 * (u & 1));
+                        }
+                    }
+                    *reinterpret_cast<u32x4_t *>(lidx + off + (int64_t)kPackChunk * rank) = w;
                 }
-                off += __popcll(m);
+                off += (int64_t)kPackChunk * __popcll(m);
             }
         }
         __syncthreads();
@@ -1785,17 +1811,28 @@ static int galerkin(const MatView &A, const int *choice, const int *chooser, Are
 #undef ORC_MERGE
     }
     lap("galerkin product");
-    int64_t *pk_ptr, *w_sell, *w_pk;
+    int64_t *pk_ptr, *lptr, *w_sell, *w_pk, *w_pos, *w_tot, *tot_ptr;
     ORC_TRY(arena.alloc((size_t)n_slices + 1, &pk_ptr));
+    ORC_TRY(arena.alloc((size_t)n_slices + 1, &lptr));
     ORC_TRY(tmp.alloc((size_t)n_slices + 1, &w_sell));
     ORC_TRY(tmp.alloc((size_t)n_slices + 1, &w_pk));
-    hipLaunchKernelGGL(slice_sizes_k, dim3((unsigned)std::min<int64_t>(((int64_t)n_slices + 3) / 4, 4096)), dim3(kBlock), 0, st, row_len, nc, n_slices, w_sell, w_pk);
+    ORC_TRY(tmp.alloc((size_t)n_slices + 1, &w_pos));
+    ORC_TRY(tmp.alloc((size_t)n_slices + 1, &w_tot));
+    ORC_TRY(arena.alloc((size_t)n_slices + 1, &tot_ptr));  // (also the row-contiguous mirror's slice starts: exact sizes, no pairs)
+    hipLaunchKernelGGL(slice_sizes_k, dim3((unsigned)std::min<int64_t>(((int64_t)n_slices + 3) / 4, 4096)), dim3(kBlock), 0, st, row_len, nc, n_slices, w_sell, w_pk,
+                       w_pos, w_tot);
     static_assert(sizeof(long long) == sizeof(int64_t), "64-bit tables");
     ORC_TRY(scan_excl_dev(reinterpret_cast<const long long *>(w_sell), reinterpret_cast<const long long *>(w_pk), (int64_t)n_slices, reinterpret_cast<long long *>(slice_ptr),
                           reinterpret_cast<long long *>(pk_ptr), true, scan_part, st));
+    ORC_TRY(scan_excl_dev(reinterpret_cast<const long long *>(w_pos), reinterpret_cast<const long long *>(w_tot), (int64_t)n_slices, reinterpret_cast<long long *>(lptr),
+                          reinterpret_cast<long long *>(tot_ptr), true, scan_part, st));
     ORC_HIP(hipGetLastError());
-    int64_t padded = 0, packed_total = 0;
-    ORC_HIP(hipMemcpyAsync(&packed_total, pk_ptr + n_slices, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    // packed_total: the entries rounded up per slice to 16 (the mirror's size before its pairs: what the choices below and the launches go by);
+    // packed_slots / pos_slots: what the mirror's values and window positions occupy
+    int64_t padded = 0, packed_total = 0, packed_slots = 0, pos_slots = 0;
+    ORC_HIP(hipMemcpyAsync(&packed_total, tot_ptr + n_slices, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ORC_HIP(hipMemcpyAsync(&packed_slots, pk_ptr + n_slices, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ORC_HIP(hipMemcpyAsync(&pos_slots, lptr + n_slices, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     ORC_HIP(hipMemcpyAsync(&padded, slice_ptr + n_slices, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     ORC_HIP(hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, st));
     ORC_HIP(hipStreamSynchronize(st));
@@ -1820,8 +1857,8 @@ static int galerkin(const MatView &A, const int *choice, const int *chooser, Are
     int *pk_col = nullptr;
     double *pk_val = nullptr;
     if (mirror) {
-        ORC_TRY(arena.alloc((size_t)packed_total, &pk_col));
-        ORC_TRY(arena.alloc((size_t)packed_total, &pk_val));
+        ORC_TRY(arena.alloc((size_t)packed_slots, &pk_col));
+        ORC_TRY(arena.alloc((size_t)packed_slots, &pk_val));
     }
     hipLaunchKernelGGL(galerkin_pack_fused_k<false>, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_slices, 256 * 12))), dim3(64), 0, st, Pc, slice_base, intra_off,
                        s_col, s_val, col, val, diag, mirror ? (const int64_t *)pk_ptr : (const int64_t *)nullptr, pk_col, pk_val);
@@ -1829,7 +1866,7 @@ static int galerkin(const MatView &A, const int *choice, const int *chooser, Are
     double *x_val[2] = {nullptr, nullptr}, *x_pk_val[2] = {nullptr, nullptr};
     for (int x = 0; x < n_sib; ++x) {  // the siblings' values on the same images
         ORC_TRY(sib[x].arena->alloc((size_t)std::max<int64_t>(padded, 1), &x_val[x]));
-        if (mirror) ORC_TRY(sib[x].arena->alloc((size_t)packed_total, &x_pk_val[x]));
+        if (mirror) ORC_TRY(sib[x].arena->alloc((size_t)packed_slots, &x_pk_val[x]));
         hipLaunchKernelGGL(galerkin_pack_fused_k<true>, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_slices, 256 * 12))), dim3(64), 0, st, Pc, slice_base, intra_off,
                            s_col, (const double *)X.s_val[x], (int *)nullptr, x_val[x], (int *)nullptr, mirror ? (const int64_t *)pk_ptr : (const int64_t *)nullptr, (int *)nullptr,
                            x_pk_val[x]);
@@ -1864,7 +1901,7 @@ static int galerkin(const MatView &A, const int *choice, const int *chooser, Are
         Lx.choice = L.choice; Lx.chooser = L.chooser;
     }
     if (!scratch) { L.rows.slice_base = slice_base; L.rows.intra_off = intra_off; L.rows.col = s_col; L.rows.val = s_val; }
-    if (scratch && packed_total > 0 && !last_level) {  // exact-size copy; the slices start where the packed mirror's do (pk_ptr); the last level is never aggregated
+    if (scratch && packed_total > 0 && !last_level) {  // exact-size copy; the slices start at the entries' offsets (tot_ptr); the last level is never aggregated
         // Only the NEXT level's aggregation and Galerkin product walk it, and the mirror of the level below (A.rows) is dead now
         // that this product's kernels are queued (same stream): both take turns in the scratch arena's companion, so a hierarchy
         // keeps no mirror once it is built (2 GB of 10.3 GB per hierarchy at 10.24 M rows).
@@ -1877,9 +1914,9 @@ static int galerkin(const MatView &A, const int *choice, const int *chooser, Are
         ORC_TRY(rows_arena.alloc(ncs, &r_intra));
         L.rows_transient = true;
         hipLaunchKernelGGL(rows_compact_k, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_slices, 256 * 16))), dim3(64), 0, st, (const int *)row_len, nc, n_slices,
-                           (const long long *)slice_base, (const int *)intra_off, (const int *)s_col, (const double *)s_val, (const int64_t *)pk_ptr, r_intra, r_col, r_val);
+                           (const long long *)slice_base, (const int *)intra_off, (const int *)s_col, (const double *)s_val, (const int64_t *)tot_ptr, r_intra, r_col, r_val);
         ORC_HIP(hipGetLastError());
-        L.rows.slice_base = reinterpret_cast<const long long *>(pk_ptr); L.rows.intra_off = r_intra; L.rows.col = r_col; L.rows.val = r_val;
+        L.rows.slice_base = reinterpret_cast<const long long *>(tot_ptr); L.rows.intra_off = r_intra; L.rows.col = r_col; L.rows.val = r_val;
         for (int x = 0; x < n_sib; ++x) {  // a whole copy per sibling: the leader's is gone when ITS next level is built
             Arena &xa = sib[x].rows_arena ? *sib[x].rows_arena : *sib[x].arena;
             if (sib[x].rows_arena) xa.release(Arena::Mark{0, 0});
@@ -1889,31 +1926,31 @@ static int galerkin(const MatView &A, const int *choice, const int *chooser, Are
             ORC_TRY(xa.alloc((size_t)packed_total, &xr_val));
             ORC_TRY(xa.alloc(ncs, &xr_intra));
             hipLaunchKernelGGL(rows_compact_k, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_slices, 256 * 16))), dim3(64), 0, st, (const int *)row_len, nc, n_slices,
-                               (const long long *)slice_base, (const int *)intra_off, (const int *)s_col, (const double *)X.s_val[x], (const int64_t *)pk_ptr, xr_intra, xr_col, xr_val);
+                               (const long long *)slice_base, (const int *)intra_off, (const int *)s_col, (const double *)X.s_val[x], (const int64_t *)tot_ptr, xr_intra, xr_col, xr_val);
             ORC_HIP(hipGetLastError());
             CoarseLevel &Lx = *sib[x].L;
-            Lx.rows.slice_base = reinterpret_cast<const long long *>(pk_ptr); Lx.rows.intra_off = xr_intra; Lx.rows.col = xr_col; Lx.rows.val = xr_val;
+            Lx.rows.slice_base = reinterpret_cast<const long long *>(tot_ptr); Lx.rows.intra_off = xr_intra; Lx.rows.col = xr_col; Lx.rows.val = xr_val;
             Lx.rows_transient = sib[x].rows_arena != nullptr;
         }
     }
     if (mirror) {
-        L.pk.ptr = pk_ptr; L.pk.col = pk_col; L.pk.val = pk_val; L.pk.total = packed_total;
+        L.pk.ptr = pk_ptr; L.pk.col = pk_col; L.pk.val = pk_val; L.pk.total = packed_total; L.pk.slots = packed_slots;
         const int64_t n_blocks = ((int64_t)n_slices + 3) / 4;
         int *wcol, *wsize;
         unsigned short *lidx;
         ORC_TRY(arena.alloc((size_t)n_blocks * kXWinCap, &wcol));
         ORC_TRY(arena.alloc((size_t)n_blocks, &wsize));
-        ORC_TRY(arena.alloc((size_t)packed_total, &lidx));
+        ORC_TRY(arena.alloc((size_t)std::max<int64_t>(pos_slots, 1), &lidx));
         const int win_cap = cfg().xwin_cap > 0 ? std::min(kXWinCap, cfg().xwin_cap) : kXWinCap;  // (test hooks: forced fallbacks)
         const int bit_words = cfg().xwin_bitwords > 0 ? std::min(kXBitWords, cfg().xwin_bitwords) : kXBitWords;
         const int small_words = cfg().xwin_small_bitwords > 0 ? std::min(kXBitWordsSmall, cfg().xwin_small_bitwords) : kXBitWordsSmall;
         int *pending;
         ORC_TRY(tmp.alloc((size_t)1, &pending));
         ORC_HIP(hipMemsetAsync(pending, 0, sizeof(int), st));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(xwin_build_k<kXBitWordsSmall, false>), dim3((unsigned)std::min<int64_t>(n_blocks, 2048)), dim3(kBlock), 0, st, Pc, L.pk, wcol, wsize, lidx,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(xwin_build_k<kXBitWordsSmall, false>), dim3((unsigned)std::min<int64_t>(n_blocks, 2048)), dim3(kBlock), 0, st, Pc, (const int64_t *)lptr, wcol, wsize, lidx,
                            n_blocks, win_cap, bit_words, small_words, pending);
         if (bit_words > small_words)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(xwin_build_k<kXBitWords, true>), dim3((unsigned)std::min<int64_t>(n_blocks, 2048)), dim3(kBlock), 0, st, Pc, L.pk, wcol, wsize, lidx,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(xwin_build_k<kXBitWords, true>), dim3((unsigned)std::min<int64_t>(n_blocks, 2048)), dim3(kBlock), 0, st, Pc, (const int64_t *)lptr, wcol, wsize, lidx,
                                n_blocks, win_cap, bit_words, kXBitWords, pending);
         if (trace_t) {
             int hp = 0;
@@ -1922,7 +1959,7 @@ static int galerkin(const MatView &A, const int *choice, const int *chooser, Are
             fprintf(stderr, "[amg windows n=%lld] %lld blocks, %d left to the full bitmap\n", (long long)nc, (long long)n_blocks, hp);
         }
         ORC_HIP(hipGetLastError());
-        L.xw.wcol = wcol; L.xw.wsize = wsize; L.xw.lidx = lidx;
+        L.xw.wcol = wcol; L.xw.wsize = wsize; L.xw.lidx = lidx; L.xw.lptr = lptr;
         {   // [r05] this level's LDS share per workgroup: the smallest of a few sizes that leaves <= 1 % of the blocks without a window
             // (+ whatever had none to begin with); one small kernel and one host read per level with windows
             int *over;
@@ -2634,6 +2671,39 @@ int amg_debug_coarsen(const MatView &A, Arena &arena, std::vector<int> &choice_h
             col_h[(size_t)(row_ptr_h[(size_t)I] + k)] = col[(size_t)(base + (int64_t)k * 64)];
             val_h[(size_t)(row_ptr_h[(size_t)I] + k)] = val[(size_t)(base + (int64_t)k * 64)];
         }
+    }
+    arena.release(mk);
+    return ORC_OK;
+}
+
+// One level of the set-up on A, as amg_debug_coarsen, and the level's packed mirror and windows copied to the host (PackedDev, XWinDev):
+// sizes = {coarse rows, slices, value slots, position slots, blocks}; with any output pointer null only the sizes are written.
+int amg_debug_packed(const MatView &A, Arena &arena, int64_t sizes[5], int32_t *row_len_h, int64_t *pk_ptr_h, int32_t *pk_col_h, double *pk_val_h,
+                     int64_t *lptr_h, uint16_t *lidx_h, int32_t *wcol_h, int32_t *wsize_h) {
+    hipStream_t st = ctx().stream;
+    Arena::Mark mk = arena.mark();
+    int *choice, *chooser;
+    const int64_t n = A.P.n;
+    ORC_TRY(arena.alloc((size_t)std::max<int64_t>(n, 1), &choice));
+    ORC_TRY(arena.alloc((size_t)std::max<int64_t>(n, 1), &chooser));
+    CoarseLevel L;
+    ORC_TRY(aggregate(A, arena, choice, chooser, &L.rounds));
+    ORC_TRY(galerkin(A, choice, chooser, arena, L));
+    const bool mirror = L.pk.ptr && L.xw.lidx;
+    const int64_t ns = L.P.n_slices, nb = (ns + 3) / 4;
+    sizes[0] = L.n; sizes[1] = ns; sizes[2] = mirror ? L.pk.slots : 0; sizes[3] = 0; sizes[4] = mirror ? nb : 0;
+    if (mirror) ORC_HIP(hipMemcpyAsync(&sizes[3], L.xw.lptr + ns, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ORC_HIP(hipStreamSynchronize(st));
+    if (mirror && row_len_h && pk_ptr_h && pk_col_h && pk_val_h && lptr_h && lidx_h && wcol_h && wsize_h) {
+        ORC_HIP(hipMemcpyAsync(row_len_h, L.P.row_len, sizeof(int32_t) * (size_t)L.n, hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipMemcpyAsync(pk_ptr_h, L.pk.ptr, sizeof(int64_t) * (size_t)(ns + 1), hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipMemcpyAsync(pk_col_h, L.pk.col, sizeof(int32_t) * (size_t)sizes[2], hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipMemcpyAsync(pk_val_h, L.pk.val, sizeof(double) * (size_t)sizes[2], hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipMemcpyAsync(lptr_h, L.xw.lptr, sizeof(int64_t) * (size_t)(ns + 1), hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipMemcpyAsync(lidx_h, L.xw.lidx, sizeof(uint16_t) * (size_t)sizes[3], hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipMemcpyAsync(wcol_h, L.xw.wcol, sizeof(int32_t) * (size_t)(nb * kXWinCap), hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipMemcpyAsync(wsize_h, L.xw.wsize, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipStreamSynchronize(st));
     }
     arena.release(mk);
     return ORC_OK;

@@ -7,6 +7,8 @@ namespace orc {
 int amg_debug_coarsen(const MatView &A, Arena &arena, std::vector<int> &choice_h, std::vector<int64_t> &row_ptr_h,
                       std::vector<int64_t> &col_h, std::vector<double> &val_h, int *rounds, const double *x_h = nullptr, double *y_h = nullptr,
                       int scaled = 0, int *mirror_out = nullptr);
+int amg_debug_packed(const MatView &A, Arena &arena, int64_t sizes[5], int32_t *row_len_h, int64_t *pk_ptr_h, int32_t *pk_col_h, double *pk_val_h,
+                     int64_t *lptr_h, uint16_t *lidx_h, int32_t *wcol_h, int32_t *wsize_h);
 int gs_debug_coloring(const SellDev &P, std::vector<int> &colors, int *n_colors);
 static SolveStats g_last_stats;
 SolveStats &last_stats() { return g_last_stats; }
@@ -210,6 +212,25 @@ int orc_debug_amg_coarse_product(int64_t n, const int64_t *row_ptr, const int64_
     std::vector<int64_t> rp, ci;
     std::vector<double> v;
     return amg_debug_coarsen(A, arena, choice, rp, ci, v, nullptr, x, y, scaled, has_window_mirror);
+}
+
+int orc_debug_amg_packed_mirror(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, const double *values, int64_t sizes[5], int32_t *row_len,
+                                int64_t *pk_ptr, int32_t *pk_col, double *pk_val, int64_t *lptr, uint16_t *lidx, int32_t *wcol, int32_t *wsize) {
+    using namespace orc;
+    ORC_TRY(ensure_init());
+    if (n < 1 || !row_ptr || !col_idx || !values || !sizes) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
+    SellMatrix pat;
+    ORC_TRY(sell_from_csr_host(n, n, row_ptr, col_idx, pat));
+    DevBuf<double> csr_vals, vals;
+    ORC_TRY(csr_vals.upload(values, (size_t)pat.nnz));
+    ORC_TRY(vals.alloc((size_t)std::max<int64_t>(pat.padded, 1)));
+    ORC_TRY(sell_import_values(pat, csr_vals.p, vals.p));
+    MatView A;
+    A.P = pat.dev();
+    A.val = vals.p;
+    A.symmetric = pat.symmetric;
+    Arena arena;
+    return amg_debug_packed(A, arena, sizes, row_len, pk_ptr, pk_col, pk_val, lptr, lidx, wcol, wsize);
 }
 
 int orc_debug_coloring(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, int32_t *colors, int32_t *n_colors) {

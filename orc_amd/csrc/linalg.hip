@@ -794,7 +794,8 @@ static inline bool materialize_scaling(uint64_t iteration_count) {
     return min_its > 0 && iteration_count >= (uint64_t)min_its;
 }
 
-// the same over a packed mirror (PackedDev): entries of depth k of a slice sit back to back in lane order
+// the same over a packed mirror (PackedDev): per pair of depths, the pairs of the lanes whose rows reach it sit back to back in lane order
+// (a row's padding slot is scaled too: it stays finite and the product drops it)
 __global__ __launch_bounds__(kBlock) void scale_packed_k(MatView A, double *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     SliceWalk w(A.P.n_slices);
@@ -805,16 +806,18 @@ __global__ __launch_bounds__(kBlock) void scale_packed_k(MatView A, double *__re
         const int len = live ? A.P.row_len[row] : 0;
         const double s1 = (A.s1 && live) ? A.s1[row] : 1.;
         const double s2 = (A.s2 && live) ? A.s2[row] : 1.;
-        int64_t off = A.pk.ptr[slice];
-        for (int k = 0; k < width; ++k) {
+        const f64x2_t *src = reinterpret_cast<const f64x2_t *>(A.pk.val + A.pk.ptr[slice]);
+        f64x2_t *dst = reinterpret_cast<f64x2_t *>(out + A.pk.ptr[slice]);
+        int off = 0;
+        for (int k = 0; k < width; k += 2) {
             const bool in = k < len;
             const unsigned long long m = __ballot(in);
             const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
             if (in) {
-                double t = A.pk.val[off + rank];
-                if (A.s1) t = s1 * t;
-                if (A.s2) t = s2 * t;
-                out[off + rank] = t;
+                f64x2_t t = src[off + rank];
+                if (A.s1) { t.x = s1 * t.x; t.y = s1 * t.y; }
+                if (A.s2) { t.x = s2 * t.x; t.y = s2 * t.y; }
+                dst[off + rank] = t;
             }
             off += __popcll(m);
         }
@@ -827,7 +830,7 @@ int materialize_scaled_view(MatView &A, uint64_t iteration_count, Arena &arena) 
         // levels with a packed mirror + LDS windows: their products stream pk.val only (launch_spmv: production variant)
         if (!(A.xw.lidx && A.pk.total > 0)) return ORC_OK;
         double *scaled;
-        ORC_TRY(arena.alloc((size_t)A.pk.total, &scaled));
+        ORC_TRY(arena.alloc((size_t)A.pk.slots, &scaled));
         hipLaunchKernelGGL(scale_packed_k, dim3(spmv_grid(A.P.n_slices)), dim3(kBlock), 0, ctx().stream, A, scaled);
         ORC_HIP(hipGetLastError());
         A.pk.val = scaled;

@@ -40,18 +40,23 @@ struct SellDev {
 };
 
 // Zero-padding mirror of a SELL-64 matrix for the wave-cooperative product (coarse AMG levels, whose rows are ragged:
-// 6-47 % of a padded SELL image is padding).  Row r keeps lane r & 63 of slice r >> 6; at depth k only the lanes whose
-// row is longer than k own an entry, and those entries are stored back to back in lane order:
-//     pos(r, k) = ptr[r >> 6] + sum_{k' < k} count(k') + |{lanes l < (r & 63) : len(l) > k}|
-// which the wavefront evaluates with a ballot, a population count and v_mbcnt per depth.  Loads stay contiguous over the
-// active lanes, every row is still summed in ascending-column order (bit-identical to the padded product), and the
-// 64 rows of a wavefront remain neighbours (no length sorting: the x gathers keep their locality).  A lone thread
-// cannot address an entry, so the padded image stays beside it for the set-up kernels that walk single rows.
+// 6-47 % of a padded SELL image is padding).  Row r keeps lane r & 63 of slice r >> 6.  The entries of a slice come in
+// chunks of 8 depths, and inside a chunk in PAIRS of depths q = 0..3 (depths 8j + 2q and 8j + 2q + 1): per pair, only the
+// lanes whose row is longer than 8j + 2q own it, and they own 16 contiguous bytes each, back to back in lane order:
+//     slot(r, k) = ptr[r >> 6] + 2 sum_{(j', q') before (j, q)} count(j', q') + 2 |{lanes l < (r & 63) : len(l) > 8j + 2q}| + (k & 1)
+// with j = k >> 3, q = (k & 7) >> 1.  A lane reads one pair with one 16-byte load (values; 8 bytes for the columns): a
+// wave-instruction reads up to 1 KiB contiguous, and the wavefront takes one ballot and v_mbcnt per pair instead of per
+// entry.  A row of odd length owns one padding slot (a finite value, 0.0, and its own row as column): it is dropped by the
+// product's select, never added.  Every row is still summed in ascending-column order (bit-identical to the padded
+// product), and the 64 rows of a wavefront remain neighbours (no length sorting: the x gathers keep their locality).  A lone
+// thread cannot address an entry, so the padded image stays beside it for the set-up kernels that walk single rows.
+constexpr int kPackChunk = 8;  // depths per chunk of the packed mirror and its window positions
 struct PackedDev {
-    const int64_t *ptr = nullptr;  // [n_slices+1] element offsets, multiples of 16 (128-byte aligned values)
+    const int64_t *ptr = nullptr;  // [n_slices+1] slot offsets, multiples of 16 (128-byte aligned values): sum of the rows' lengths rounded up to even
     const int32_t *col = nullptr;
     const double *val = nullptr;
-    int64_t total = 0;             // stored entries (ptr[n_slices]) when the host knows it, else 0
+    int64_t total = 0;             // stored entries rounded up per slice to 16 (what the launches decide by) when the host knows it, else 0
+    int64_t slots = 0;             // slots of col / val (ptr[n_slices]), >= total by the pairs' padding
 };
 
 // LDS-staged x tiles for the packed mirror (BASELINE north star: "LDS-staged x-vector tiles").  Rows are taken in
@@ -67,7 +72,11 @@ constexpr int kXWinCap = 5000;   // window entries per block: 40 KB of LDS, four
 struct XWinDev {
     const int32_t *wcol = nullptr;   // [n_blocks * kXWinCap]
     const int32_t *wsize = nullptr;  // [n_blocks], -1 = no window for this block
-    const uint16_t *lidx = nullptr;  // [packed entries] window position of the entry's column
+    // window positions of the packed entries, per chunk of 8 depths: every lane whose row is longer than 8j owns 8 contiguous positions
+    // (16 bytes: one load), back to back in lane order; the positions past the row's end are 0 (a valid window entry, dropped by the select):
+    //     pos(r, k) = lptr[r >> 6] + 8 sum_{j' < j} count(j') + 8 |{lanes l < (r & 63) : len(l) > 8j}| + (k & 7),  j = k >> 3
+    const uint16_t *lidx = nullptr;  // [lptr[n_slices]]
+    const int64_t *lptr = nullptr;   // [n_slices+1] offsets of the slices' positions, multiples of 64 (128 bytes)
     // [r05] the LDS entries a product of THIS level provides per workgroup (<= kXWinCap): the smallest of a few sizes that leaves <= 1 % of the
     // level's blocks without a window.  The compiled worst case (5 000 entries = 40 KB) held a CU to four workgroups whatever the level needed
     // (the channel's level 2: 2 200 per block); blocks whose window is larger gather from global memory, as blocks without a window always did.

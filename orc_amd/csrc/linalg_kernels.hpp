@@ -24,6 +24,21 @@ __device__ __forceinline__ T ld_stream(const T *p) {
     return *p;
 }
 
+// the packed mirror's 16-byte (and 8-byte) units: one load per lane and pair of values / chunk of window positions (PackedDev, XWinDev)
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+typedef int i32x2_t __attribute__((ext_vector_type(2)));
+typedef double f64x2_t __attribute__((ext_vector_type(2)));
+
+// The lane's slot (in pairs) of pair group `in` of a packed slice whose group starts at pair `off`; idle lanes read a stored
+// neighbour (the group's first pair, or the pair before an empty group: loads stay unconditional, see spmv_k).  Advances off.
+__device__ __forceinline__ int packed_pair(bool in, int &off) {
+    const unsigned long long m = __ballot(in);
+    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    const int p = in ? off + rank : (m != 0ull ? off : off - 1);
+    off += __popcll(m);
+    return p;
+}
+
 // The same fold done by EVERY workgroup of the kernel that consumes the sum (256 threads): four passes over
 // reduce_partials_k's 16 virtual wavefronts, so the association — and therefore every bit — is that of the one-workgroup
 // kernel.  A BiCGSTAB iteration has three such sums; as separate one-workgroup launches they sit between the big kernels
@@ -159,7 +174,10 @@ __global__ __launch_bounds__(kBlock) void spmv_k(MatView A, const double *__rest
         // predicated loads compile into one exec-masked branch each with an s_waitcnt behind every column load, i.e.
         // eight serialised round trips per chunk — that, not padding or the x gathers, is what held the ragged coarse
         // levels at 36-48 % of peak.
-        int64_t pk_off = kLayout == kSpmvPacked ? A.pk.ptr[slice] : 0;  // wave-uniform running offset of depth k0
+        // packed: the slice's pairs (PackedDev), a wave-uniform running pair offset inside the slice
+        const i32x2_t *pk_c = kLayout == kSpmvPacked ? reinterpret_cast<const i32x2_t *>(A.pk.col + A.pk.ptr[slice]) : nullptr;
+        const f64x2_t *pk_v = kLayout == kSpmvPacked ? reinterpret_cast<const f64x2_t *>(A.pk.val + A.pk.ptr[slice]) : nullptr;
+        int pk_off = 0;
         const int last = (kLayout == kSpmvRagged ? (len > 0 ? len : 1) : width) - 1;  // deepest slot this lane may touch
         // lanes past the last row of the matrix (last slice only) re-read the last row's slots: their own were never
         // written by the device-side pack kernels, and an unconditional gather through a garbage column would fault
@@ -167,31 +185,33 @@ __global__ __launch_bounds__(kBlock) void spmv_k(MatView A, const double *__rest
         for (int k0 = 0; k0 < width; k0 += 8) {
             int c[8];
             double v[8], xv[8];
+            if (kLayout == kSpmvPacked) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (kLayout == kSpmvPacked) {
-                    // entries of depth k0 + u: one per lane whose row is long enough, back to back in lane order
-                    const bool in = k0 + u < len;
-                    const unsigned long long m = __ballot(in);
-                    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                    const int64_t p = in ? pk_off + rank : (m != 0ull ? pk_off : pk_off - 1);  // idle lanes: a stored neighbour
-                    c[u] = A.pk.col[p];
-                    v[u] = A.pk.val[p];
-                    pk_off += __popcll(m);
-                } else if (kGuard) {
-                    if (k0 + u < width) {  // wave-uniform
-                        // padded layout: the slot exists for every lane, so its address is the chunk base plus a compile-time
-                        // offset (folded into the load instruction); only the predicated layout has to clamp per lane
-                        const int kk = kLayout == kSpmvPlain ? k0 + u : (k0 + u < last ? k0 + u : last);
-                        const int64_t p = kLayout == kSpmvPlain ? (base + (int64_t)k0 * 64 + lane_c) + (int64_t)u * 64 : base + (int64_t)kk * 64 + lane_c;
+                for (int q = 0; q < 4; ++q) {  // depths k0 + 2q, k0 + 2q + 1: one pair per lane whose row is long enough
+                    const int p = packed_pair(k0 + 2 * q < len, pk_off);
+                    const i32x2_t cc = pk_c[p];
+                    const f64x2_t vv = pk_v[p];
+                    c[2 * q] = cc.x; c[2 * q + 1] = cc.y;
+                    v[2 * q] = vv.x; v[2 * q + 1] = vv.y;
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    if (kGuard) {
+                        if (k0 + u < width) {  // wave-uniform
+                            // padded layout: the slot exists for every lane, so its address is the chunk base plus a compile-time
+                            // offset (folded into the load instruction); only the predicated layout has to clamp per lane
+                            const int kk = kLayout == kSpmvPlain ? k0 + u : (k0 + u < last ? k0 + u : last);
+                            const int64_t p = kLayout == kSpmvPlain ? (base + (int64_t)k0 * 64 + lane_c) + (int64_t)u * 64 : base + (int64_t)kk * 64 + lane_c;
+                            c[u] = A.P.col[p];
+                            v[u] = A.val[p];
+                        } else { c[u] = 0; v[u] = 0.; }
+                    } else {
+                        const int kk = k0 + u < last ? k0 + u : last;
+                        const int64_t p = base + (int64_t)kk * 64 + lane_c;
                         c[u] = A.P.col[p];
                         v[u] = A.val[p];
-                    } else { c[u] = 0; v[u] = 0.; }
-                } else {
-                    const int kk = k0 + u < last ? k0 + u : last;
-                    const int64_t p = base + (int64_t)kk * 64 + lane_c;
-                    c[u] = A.P.col[p];
-                    v[u] = A.val[p];
+                    }
                 }
             }
 #pragma unroll
@@ -379,70 +399,21 @@ __global__ __launch_bounds__(kBlock) void spmv3_uniform_k(MatView3 A, const doub
     }
 }
 
-// The same product software-pipelined across chunks AND slices: the column/value loads of the next chunk (of the same
-// slice or of the wave's next slice) are issued right behind the current chunk's x gathers, so a wave's HBM round trip
-// overlaps its gather round trip instead of following it (vmcnt counts in order: gathers first, then the younger
-// prefetches, so the wait for the gathers leaves the prefetches in flight).  Same rows, same order, same sums.
-template <int kLayout>
-struct SpmvSliceMeta {
-    int64_t base, row, pk_off;
-    int width, len, last;
-    bool live;
-    double s1, s2;
-    int lane_c;
-    __device__ __forceinline__ void load(const MatView &A, int64_t slice, int lane) {
-        row = slice * 64 + lane;
-        lane_c = row < A.P.n ? lane : (int)((A.P.n - 1) & 63);
-        base = A.P.slice_ptr[slice];
-        width = (int)((A.P.slice_ptr[slice + 1] - base) >> 6);
-        live = row < A.P.n;
-        len = live ? A.P.row_len[row] : 0;
-        s1 = (A.s1 && live) ? A.s1[row] : 1.;
-        s2 = (A.s2 && live) ? A.s2[row] : 1.;
-        pk_off = kLayout == kSpmvPacked ? A.pk.ptr[slice] : 0;
-        last = (kLayout == kSpmvRagged ? (len > 0 ? len : 1) : width) - 1;
-    }
-    // issues the 16 loads of chunk k0 (branch-free, see spmv_k); advances the packed offset
-    __device__ __forceinline__ void issue(const MatView &A, int k0, int lane, int (&c)[8], double (&v)[8]) {
-        if (width <= 0) {  // wave-uniform: an all-empty slice owns no storage
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { c[u] = 0; v[u] = 0.; }
-            return;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            if (kLayout == kSpmvPacked) {
-                const bool in = k0 + u < len;
-                const unsigned long long m = __ballot(in);
-                const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                const int64_t p = in ? pk_off + rank : (m != 0ull ? pk_off : pk_off - 1);
-                c[u] = A.pk.col[p];
-                v[u] = A.pk.val[p];
-                pk_off += __popcll(m);
-            } else {
-                const int kk = k0 + u < last ? k0 + u : last;
-                const int64_t p = base + (int64_t)kk * 64 + lane_c;
-                c[u] = A.P.col[p];
-                v[u] = A.val[p];
-            }
-        }
-    }
-};
-
 // Product on the packed mirror with LDS-staged x windows (XWinDev): one workgroup per block of 256 rows, its 4 waves on
 // the block's 4 slices.  Workgroups b and b + 8 share an XCD, so XCD g walks a contiguous eighth of the blocks.
 // kScaled = false: the view carries no row scaling (a smoothing solve has materialised its scaled values, materialize_scaled_view):
 // the two scaling multiplications per entry and their selects are not compiled in — the stream loop of this kernel is bound by
 // instruction issue as much as by memory (39 vector instructions per entry and wavefront, profiles/r03_pmc_products.csv)
-// kC: entries per lane and chunk of the stream (two chunks in flight): 8 = 92-94 VGPRs, five workgroups per CU where the level's LDS share
-// (XWinDev::cap) allows them.  [r05] measured: 4 (58 VGPRs, up to 24 wavefronts per CU on the level whose windows fit 25 KB) is no faster — 233.1 /
-// 226.6 against 226.2 / 227.5 us on that level, 226.4 / 219.7 against 224.9 / 218.6 on the last (scripts/archive/gpu_r05_j.sh): like the per-level LDS
-// share itself (16 -> 20 wavefronts per CU: -1 ... -3 %), occupancy is not what holds this product at 4.6-4.8 TB/s
-template <class Epi, bool kScaled = true, bool kNT = false, int kC = 8>
+// Two chunks of kC = 8 entries (the mirror's chunk) in flight per lane.  [r05] measured with the depth-major mirror: 4 entries per chunk (58 VGPRs, up to
+// 24 wavefronts per CU) was no faster than 8 (92-94 VGPRs) — 233.1 / 226.6 against 226.2 / 227.5 us on level 2, 226.4 / 219.7 against 224.9 / 218.6 on
+// level 3 (scripts/archive/gpu_r05_j.sh): like the per-level LDS share itself (16 -> 20 wavefronts per CU: -1 ... -3 %), occupancy is not what held this
+// product at 4.6-4.8 TB/s; the number of load instructions per entry was (scripts/microbench/xwin_layout.hip)
+template <class Epi, bool kScaled = true, bool kNT = false>
 __global__ __launch_bounds__(kBlock) void spmv_xwin_k(MatView A, const double *__restrict__ x, Epi epi, double *__restrict__ partials,
                                                       const double *__restrict__ skip_flags) {
     __shared__ double lds[8];
     extern __shared__ __align__(16) double xs[];  // A.xw.cap entries (dynamic: sized per level by the launch)
+    constexpr int kC = kPackChunk;
     if (skip_flags && (skip_flags[0] != 0. || skip_flags[1] != 0.)) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (scalar: the slice's descriptors go through the scalar cache)
     double r0 = 0., r1 = 0.;
@@ -467,32 +438,35 @@ __global__ __launch_bounds__(kBlock) void spmv_xwin_k(MatView A, const double *_
         const int64_t row = slice * 64 + lane;
         const bool live = has_slice && row < A.P.n;
         int width = 0, len = 0;
-        int64_t pk_off = 0;
+        int64_t pk_off = 0, lp_off = 0;
         if (has_slice) {
             const int64_t base = A.P.slice_ptr[slice];
             width = (int)((A.P.slice_ptr[slice + 1] - base) >> 6);
             len = live ? A.P.row_len[row] : 0;
             pk_off = A.pk.ptr[slice];
+            lp_off = ws >= 0 ? A.xw.lptr[slice] : 0;
         }
         // Addresses are a wave-uniform slice base (scalar registers) plus a 32-bit in-slice offset: no 64-bit vector arithmetic
         // per entry.
         const int64_t sb = __builtin_amdgcn_readfirstlane((int)(pk_off & 0xffffffff)) | ((int64_t)__builtin_amdgcn_readfirstlane((int)(pk_off >> 32)) << 32);
-        const unsigned short *s_lidx = A.xw.lidx + sb;
-        const double *s_val = A.pk.val + sb;
-        int off32 = 0;  // wave-uniform running offset of the chunk inside the slice
-        int c[kC], cn[kC];
-        double v[kC], vn[kC];
-        auto issue = [&](int k0, int (&cc)[kC], double (&vv)[kC]) {
-#pragma unroll
-            for (int u = 0; u < kC; ++u) {  // branch-free loads, see spmv_k
-                const bool in = k0 + u < len;
-                const unsigned long long m = __ballot(in);
+        const int64_t lb = __builtin_amdgcn_readfirstlane((int)(lp_off & 0xffffffff)) | ((int64_t)__builtin_amdgcn_readfirstlane((int)(lp_off >> 32)) << 32);
+        const u32x4_t *s_pos = reinterpret_cast<const u32x4_t *>(A.xw.lidx + lb);  // one per chunk and live lane
+        const f64x2_t *s_val = reinterpret_cast<const f64x2_t *>(A.pk.val + sb);   // one per pair and live lane
+        int poff = 0, voff = 0;  // wave-uniform running offsets inside the slice, in chunks of positions / pairs of values
+        // [r06] One chunk of kC = 8 entries is one 16-byte position load and four 16-byte value loads per lane (PackedDev, XWinDev: lane-major
+        // chunks), one ballot per pair: 5 vector-memory instructions per 8 entries instead of 16 — the depth-major mirror's loads were 2 and 8
+        // bytes per lane, and this loop is bound by instruction issue as much as by memory (TA busy 76-83 %)
+        u32x4_t c, cn;
+        f64x2_t v[kC / 2], vn[kC / 2];
+        auto issue = [&](int k0, u32x4_t &cc, f64x2_t (&vv)[kC / 2]) {  // branch-free loads, see spmv_k
+            {
+                const unsigned long long m = __ballot(k0 < len);
                 const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                const int p = in ? off32 + rank : (m != 0ull ? off32 : off32 - 1);
-                cc[u] = (int)ld_stream<kNT>(s_lidx + p);
-                vv[u] = ld_stream<kNT>(s_val + p);
-                off32 += __popcll(m);
+                cc = ld_stream<kNT>(s_pos + poff + (k0 < len ? rank : 0));  // (a chunk below the slice width has a live lane: its first slot exists)
+                poff += __popcll(m);
             }
+#pragma unroll
+            for (int q = 0; q < kC / 2; ++q) vv[q] = ld_stream<kNT>(s_val + packed_pair(k0 + 2 * q < len, voff));
         };
         if (ws > 0) {
             // window -> LDS: all column loads of a pass are issued before the x gathers, those before the LDS writes
@@ -527,13 +501,17 @@ __global__ __launch_bounds__(kBlock) void spmv_xwin_k(MatView A, const double *_
                 // pass, and a copy reads its source — `s_waitcnt vmcnt(0)` in front of the copies (listing), i.e. every pass ended by
                 // waiting for the chunk it had just requested.  Now the two register sets take turns (the loop is unrolled by two): a pass
                 // waits for the OLDER chunk only (vmcnt retires in order), the younger one travels while it is multiplied.
-                auto consume = [&](int k0, const int (&cc)[kC], const double (&vv)[kC]) {
+                auto consume = [&](int k0, const u32x4_t &cc, const f64x2_t (&vv)[kC / 2]) {
                     double xv[kC];
 #pragma unroll
-                    for (int u = 0; u < kC; ++u) xv[u] = xs[cc[u]];
+                    for (int q = 0; q < kC / 2; ++q) {
+                        const unsigned w = cc[q];
+                        xv[2 * q] = xs[w & 0xffffu];
+                        xv[2 * q + 1] = xs[w >> 16];
+                    }
 #pragma unroll
                     for (int u = 0; u < kC; ++u) {
-                        double t = vv[u];
+                        double t = vv[u >> 1][u & 1];
                         if (kScaled && A.s1) t = s1 * t;
                         if (kScaled && A.s2) t = s2 * t;
                         const double next = acc + t * xv[u];
@@ -550,18 +528,17 @@ __global__ __launch_bounds__(kBlock) void spmv_xwin_k(MatView A, const double *_
                 }
                 if (k0 < width) consume(k0, c, v);
             } else {
+                const i32x2_t *s_col = reinterpret_cast<const i32x2_t *>(A.pk.col + sb);
                 for (int k0 = 0; k0 < width; k0 += 8) {
                     int cg[8];
                     double vg[8], xv[8];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const bool in = k0 + u < len;
-                        const unsigned long long m = __ballot(in);
-                        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                        const int64_t p = in ? pk_off + rank : (m != 0ull ? pk_off : pk_off - 1);
-                        cg[u] = ld_stream<kNT>(A.pk.col + p);
-                        vg[u] = ld_stream<kNT>(A.pk.val + p);
-                        pk_off += __popcll(m);
+                    for (int q = 0; q < 4; ++q) {
+                        const int p = packed_pair(k0 + 2 * q < len, voff);
+                        const i32x2_t cc = ld_stream<kNT>(s_col + p);
+                        const f64x2_t vv = ld_stream<kNT>(s_val + p);
+                        cg[2 * q] = cc.x; cg[2 * q + 1] = cc.y;
+                        vg[2 * q] = vv.x; vg[2 * q + 1] = vv.y;
                     }
 #pragma unroll
                     for (int u = 0; u < 8; ++u) xv[u] = x[cg[u]];

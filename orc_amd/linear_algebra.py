@@ -150,6 +150,28 @@ def amg_coarse_product(a, x, scaled=False):
     return y, bool(mirror.value)
 
 
+def amg_packed_mirror(a):
+    """Test hook: the coarse level of a (as amg_coarsen builds it) as its products read it — the packed mirror and the LDS x windows.
+    Returns None when the level has no mirror, else a dict of row_len, pk_ptr, pk_col, pk_val, lptr, lidx, wcol ([blocks, 5000]), wsize."""
+    a = a.tocsr()
+    a.sort_indices()
+    n = a.shape[0]
+    rp, ci, v = _i64(a.indptr), _i64(a.indices), _f64(a.data)
+    sizes = np.zeros(5, np.int64)
+    f = lib().orc_debug_amg_packed_mirror
+    null = [None] * 8
+    check(f(C.c_int64(n), _p(rp, C.c_int64), _p(ci, C.c_int64), _p(v, C.c_double), _p(sizes, C.c_int64), *null))
+    nc, ns, slots, pos_slots, nb = (int(t) for t in sizes)
+    if slots == 0:
+        return None
+    out = dict(row_len=np.empty(nc, np.int32), pk_ptr=np.empty(ns + 1, np.int64), pk_col=np.empty(slots, np.int32), pk_val=np.empty(slots),
+               lptr=np.empty(ns + 1, np.int64), lidx=np.empty(pos_slots, np.uint16), wcol=np.empty((nb, 5000), np.int32), wsize=np.empty(nb, np.int32))
+    check(f(C.c_int64(n), _p(rp, C.c_int64), _p(ci, C.c_int64), _p(v, C.c_double), _p(sizes, C.c_int64), _p(out["row_len"], C.c_int32),
+            _p(out["pk_ptr"], C.c_int64), _p(out["pk_col"], C.c_int32), _p(out["pk_val"], C.c_double), _p(out["lptr"], C.c_int64),
+            _p(out["lidx"], C.c_uint16), _p(out["wcol"], C.c_int32), _p(out["wsize"], C.c_int32)))
+    return out
+
+
 def xwin_counters(reset=False):
     """Test hook: (blocks described, blocks without a window because of the cap, ... because of the column span) since the last reset"""
     out = (C.c_longlong * 3)()

@@ -1,0 +1,356 @@
+// xwin_layout.hip — the window product's matrix stream (spmv_xwin_k) in two layouts of the packed mirror, at equal work:
+//   depth-major: depth k of a slice holds the live lanes back to back (one ballot, two mbcnt, a 2-byte position load and an
+//                8-byte value load per entry: 16 vector-memory instructions per 8 entries);
+//   chunked:     per chunk of 8 depths every live lane owns 16 contiguous bytes of positions (8 x u16) and, per pair of depths q,
+//                16 contiguous bytes of values ([q][lane][2 doubles], lanes compacted per pair): 5 dwordx4 loads per 8 entries.
+// A synthetic coarse level: `rows` rows of uniformly random length in [lo, hi], one workgroup per block of 256 rows, a window of
+// `ws` sorted columns per block staged in LDS, positions random in the window.  Both kernels add every row in ascending k with the
+// same select, so y must agree bit for bit.  --global: no window, 32-bit columns and global x gathers (the level-1 question).
+// Build: hipcc --offload-arch=gfx950 -O3 xwin_layout.hip -o xwin_layout
+//   ./xwin_layout [rows lo hi ws reps [--global]]      (defaults: the channel's level 2 shape, 2 560 000 rows, 25-55 entries, 2 560)
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
+
+struct Mat {
+    int64_t n, n_slices;
+    const int *len, *width;
+    const int64_t *ptr;              // depth-major: slice starts (entries)
+    const int64_t *pptr, *vptr;      // chunked: slice starts of positions (u16) and values (doubles)
+    const unsigned short *lidx;      // positions (either layout)
+    const int *col;                  // --global: 32-bit columns in the value layout
+    const double *val;
+    const int *wcol, *wsize;
+    int cap;
+};
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+template <class T>
+__device__ __forceinline__ T ldnt(const T *p) { return __builtin_nontemporal_load(p); }
+
+__device__ __forceinline__ void load_window(const Mat &A, int64_t b, const double *__restrict__ x, double *xs) {
+    const int ws = A.wsize[b];
+    const int *wc = A.wcol + b * A.cap;
+    for (int j0 = 0; j0 < ws; j0 += 8 * 256) {
+        int wj[8];
+        double xw[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { const int j = j0 + q * 256 + (int)threadIdx.x; wj[q] = ldnt(wc + (j < ws ? j : 0)); }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) xw[q] = x[wj[q]];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { const int j = j0 + q * 256 + (int)threadIdx.x; if (j < ws) xs[j] = xw[q]; }
+    }
+}
+
+// the production loop (linalg_kernels.hpp spmv_xwin_k, kScaled = false, kNT = true, kC = 8), EpiStore
+template <bool kGlobal>
+__global__ __launch_bounds__(256) void depth_major_k(Mat A, const double *__restrict__ x, double *__restrict__ y) {
+    extern __shared__ __align__(16) double xs[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t n_blocks = (A.n_slices + 3) >> 2;
+    for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        if (!kGlobal) load_window(A, b, x, xs);
+        __syncthreads();
+        const int64_t slice = b * 4 + wave;
+        if (slice < A.n_slices) {
+            const int64_t row = slice * 64 + lane;
+            const bool live = row < A.n;
+            const int width = A.width[slice], len = live ? A.len[row] : 0;
+            const int64_t pk_off = A.ptr[slice];
+            const int64_t sb = __builtin_amdgcn_readfirstlane((int)(pk_off & 0xffffffff)) | ((int64_t)__builtin_amdgcn_readfirstlane((int)(pk_off >> 32)) << 32);
+            const unsigned short *s_lidx = A.lidx + sb;
+            const int *s_col = A.col + sb;
+            const double *s_val = A.val + sb;
+            int off32 = 0;
+            int c[8], cn[8];
+            double v[8], vn[8], acc = 0.;
+            auto issue = [&](int k0, int (&cc)[8], double (&vv)[8]) {
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const bool in = k0 + u < len;
+                    const unsigned long long m = __ballot(in);
+                    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                    const int p = in ? off32 + rank : (m != 0ull ? off32 : off32 - 1);
+                    cc[u] = kGlobal ? ldnt(s_col + p) : (int)ldnt(s_lidx + p);
+                    vv[u] = ldnt(s_val + p);
+                    off32 += __popcll(m);
+                }
+            };
+            auto consume = [&](int k0, const int (&cc)[8], const double (&vv)[8]) {
+                double xv[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) xv[u] = kGlobal ? x[cc[u]] : xs[cc[u]];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { const double next = acc + vv[u] * xv[u]; acc = (k0 + u < len) ? next : acc; }
+            };
+            if (width > 0) issue(0, c, v);
+            int k0 = 0;
+            for (; k0 + 8 < width; k0 += 16) {
+                issue(k0 + 8, cn, vn);
+                consume(k0, c, v);
+                if (k0 + 16 < width) issue(k0 + 16, c, v);
+                consume(k0 + 8, cn, vn);
+            }
+            if (k0 < width) consume(k0, c, v);
+            if (live) y[row] = acc;
+        }
+        __syncthreads();
+    }
+}
+
+// chunked lane-major layout: 1 + 4 sixteen-byte loads per chunk of 8 entries (--global: 4 x 8-byte column loads instead of the positions)
+struct Chunk {
+    u32x4 p;         // 8 positions
+    i32x2 cg[4];      // --global: columns of pair q
+    f64x2 v[4];    // values of pair q
+};
+
+template <bool kGlobal>
+__global__ __launch_bounds__(256) void chunked_k(Mat A, const double *__restrict__ x, double *__restrict__ y) {
+    extern __shared__ __align__(16) double xs[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t n_blocks = (A.n_slices + 3) >> 2;
+    for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        if (!kGlobal) load_window(A, b, x, xs);
+        __syncthreads();
+        const int64_t slice = b * 4 + wave;
+        if (slice < A.n_slices) {
+            const int64_t row = slice * 64 + lane;
+            const bool live = row < A.n;
+            const int width = A.width[slice], len = live ? A.len[row] : 0;
+            const int64_t po = A.pptr[slice], vo = A.vptr[slice];
+            const int64_t psb = __builtin_amdgcn_readfirstlane((int)(po & 0xffffffff)) | ((int64_t)__builtin_amdgcn_readfirstlane((int)(po >> 32)) << 32);
+            const int64_t vsb = __builtin_amdgcn_readfirstlane((int)(vo & 0xffffffff)) | ((int64_t)__builtin_amdgcn_readfirstlane((int)(vo >> 32)) << 32);
+            const u32x4 *s_pos = reinterpret_cast<const u32x4 *>(A.lidx + psb);   // one u32x4 per (chunk, live lane)
+            const f64x2 *s_val = reinterpret_cast<const f64x2 *>(A.val + vsb);  // one f64x2 per (chunk, pair, live lane)
+            const i32x2 *s_col = reinterpret_cast<const i32x2 *>(A.col + vsb);
+            int poff = 0, voff = 0;  // wave-uniform running offsets in 16-byte (positions / value pairs) units
+            Chunk c, cn;
+            double acc = 0.;
+            auto issue = [&](int k0, Chunk &ch) {
+                if (!kGlobal) {
+                    const bool in = k0 < len;
+                    const unsigned long long m = __ballot(in);
+                    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                    ch.p = ldnt(s_pos + poff + (in ? rank : 0));  // (a chunk below the slice width has a live lane: slot 0 exists)
+                    poff += __popcll(m);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const bool in = k0 + 2 * q < len;
+                    const unsigned long long m = __ballot(in);
+                    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                    const int p = in ? voff + rank : (m != 0ull ? voff : voff - 1);
+                    if (kGlobal) ch.cg[q] = ldnt(s_col + p);
+                    ch.v[q] = ldnt(s_val + p);
+                    voff += __popcll(m);
+                }
+            };
+            auto consume = [&](int k0, const Chunk &ch) {
+                double xv[8];
+                if (kGlobal) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { xv[2 * q] = x[ch.cg[q].x]; xv[2 * q + 1] = x[ch.cg[q].y]; }
+                } else {
+                    const unsigned w[4] = {ch.p.x, ch.p.y, ch.p.z, ch.p.w};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { xv[2 * q] = xs[w[q] & 0xffffu]; xv[2 * q + 1] = xs[w[q] >> 16]; }
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double n0 = acc + ch.v[q].x * xv[2 * q];
+                    acc = (k0 + 2 * q < len) ? n0 : acc;
+                    const double n1 = acc + ch.v[q].y * xv[2 * q + 1];
+                    acc = (k0 + 2 * q + 1 < len) ? n1 : acc;
+                }
+            };
+            if (width > 0) issue(0, c);
+            int k0 = 0;
+            for (; k0 + 8 < width; k0 += 16) {
+                issue(k0 + 8, cn);
+                consume(k0, c);
+                if (k0 + 16 < width) issue(k0 + 16, c);
+                consume(k0 + 8, cn);
+            }
+            if (k0 < width) consume(k0, c);
+            if (live) y[row] = acc;
+        }
+        __syncthreads();
+    }
+}
+
+static inline uint64_t mix(uint64_t z) {
+    z += 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+int main(int argc, char **argv) {
+    const int64_t n = argc > 1 ? atoll(argv[1]) : 2560000;
+    const int lo = argc > 2 ? atoi(argv[2]) : 25, hi = argc > 3 ? atoi(argv[3]) : 55;
+    const int ws = argc > 4 ? atoi(argv[4]) : 2560;
+    const int reps = argc > 5 ? atoi(argv[5]) : 20;
+    const bool global = argc > 6 && !strcmp(argv[6], "--global");
+    const int64_t n_slices = (n + 63) / 64, n_blocks = (n_slices + 3) / 4;
+    std::vector<int> len(n), width(n_slices, 0);
+    for (int64_t r = 0; r < n; ++r) {
+        len[r] = lo + (int)(mix(r) % (uint64_t)(hi - lo + 1));
+        width[r / 64] = std::max(width[r / 64], len[r]);
+    }
+    auto pos_of = [&](int64_t r, int k) { return (unsigned short)(mix(r * 131 + k + 7) % (uint64_t)ws); };
+    auto col_of = [&](int64_t r, int k) { return (int)(mix(r * 131 + k + 7) % (uint64_t)n); };
+    auto val_of = [&](int64_t r, int k) { return 1.0 + (double)(mix(r * 977 + k) % 1000) * 1e-3; };
+    // depth-major
+    std::vector<int64_t> ptr(n_slices + 1, 0);
+    for (int64_t s = 0; s < n_slices; ++s) {
+        int64_t e = 0;
+        for (int l = 0; l < 64 && s * 64 + l < n; ++l) e += len[s * 64 + l];
+        ptr[s + 1] = ptr[s] + ((e + 15) & ~(int64_t)15);
+    }
+    // chunked: positions in 8-entry granules per live lane and chunk, values in 2-entry granules per live lane and pair
+    std::vector<int64_t> pptr(n_slices + 1, 0), vptr(n_slices + 1, 0);
+    for (int64_t s = 0; s < n_slices; ++s) {
+        int64_t pe = 0, ve = 0;
+        for (int l = 0; l < 64 && s * 64 + l < n; ++l) { pe += 8 * ((len[s * 64 + l] + 7) / 8); ve += 2 * ((len[s * 64 + l] + 1) / 2); }
+        pptr[s + 1] = pptr[s] + ((pe + 63) & ~(int64_t)63);
+        vptr[s + 1] = vptr[s] + ((ve + 15) & ~(int64_t)15);
+    }
+    const int64_t e_old = ptr[n_slices], pe_new = pptr[n_slices], ve_new = vptr[n_slices];
+    int64_t nnz = 0;
+    for (int64_t r = 0; r < n; ++r) nnz += len[r];
+    std::vector<unsigned short> lidx_o(e_old), lidx_n(pe_new, 0);
+    std::vector<int> col_o(global ? e_old : 1), col_n(global ? ve_new : 2, 0);
+    std::vector<double> val_o(e_old), val_n(ve_new, 0.);
+    for (int64_t s = 0; s < n_slices; ++s) {
+        int64_t off = ptr[s];
+        for (int k = 0; k < width[s]; ++k)
+            for (int l = 0; l < 64 && s * 64 + l < n; ++l) {
+                const int64_t r = s * 64 + l;
+                if (k >= len[r]) continue;
+                lidx_o[off] = pos_of(r, k); val_o[off] = val_of(r, k);
+                if (global) col_o[off] = col_of(r, k);
+                ++off;
+            }
+        int64_t po = pptr[s], vo = vptr[s];
+        for (int j = 0; j < (width[s] + 7) / 8; ++j) {
+            for (int l = 0; l < 64 && s * 64 + l < n; ++l) {
+                const int64_t r = s * 64 + l;
+                if (8 * j >= len[r]) continue;
+                for (int u = 0; u < 8; ++u) lidx_n[po + u] = 8 * j + u < len[r] ? pos_of(r, 8 * j + u) : 0;
+                po += 8;
+            }
+            for (int q = 0; q < 4; ++q)
+                for (int l = 0; l < 64 && s * 64 + l < n; ++l) {
+                    const int64_t r = s * 64 + l;
+                    const int k = 8 * j + 2 * q;
+                    if (k >= len[r]) continue;
+                    for (int t = 0; t < 2; ++t) {
+                        val_n[vo + t] = k + t < len[r] ? val_of(r, k + t) : 0.;
+                        if (global) col_n[vo + t] = k + t < len[r] ? col_of(r, k + t) : 0;
+                    }
+                    vo += 2;
+                }
+        }
+    }
+    // windows: `ws` ascending columns around the block's rows
+    std::vector<int> wcol((size_t)n_blocks * ws), wsize(n_blocks, global ? -1 : ws);
+    for (int64_t b = 0; b < n_blocks; ++b) {
+        int64_t c = std::max<int64_t>(0, std::min<int64_t>(b * 256 - ws, n - 3 * (int64_t)ws));
+        for (int j = 0; j < ws; ++j) { c += 1 + (int)(mix(b * 5000 + j) % 3); wcol[b * ws + j] = (int)std::min<int64_t>(c, n - 1); }
+    }
+    std::vector<double> xh(n);
+    for (int64_t i = 0; i < n; ++i) xh[i] = 0.5 + (double)(mix(i + 99) % 1000) * 1e-3;
+
+    Mat A{};
+    A.n = n; A.n_slices = n_slices; A.cap = ws;
+    int *d_len, *d_width, *d_wcol, *d_wsize, *d_col_o, *d_col_n;
+    int64_t *d_ptr, *d_pptr, *d_vptr;
+    unsigned short *d_lo, *d_ln;
+    double *d_vo, *d_vn, *d_x, *d_y0, *d_y1;
+    CK(hipMalloc(&d_len, n * 4)); CK(hipMalloc(&d_width, n_slices * 4));
+    CK(hipMalloc(&d_wcol, wcol.size() * 4)); CK(hipMalloc(&d_wsize, n_blocks * 4));
+    CK(hipMalloc(&d_ptr, (n_slices + 1) * 8)); CK(hipMalloc(&d_pptr, (n_slices + 1) * 8)); CK(hipMalloc(&d_vptr, (n_slices + 1) * 8));
+    CK(hipMalloc(&d_lo, e_old * 2)); CK(hipMalloc(&d_ln, pe_new * 2));
+    CK(hipMalloc(&d_col_o, col_o.size() * 4)); CK(hipMalloc(&d_col_n, col_n.size() * 4));
+    CK(hipMalloc(&d_vo, e_old * 8)); CK(hipMalloc(&d_vn, ve_new * 8));
+    CK(hipMalloc(&d_x, n * 8)); CK(hipMalloc(&d_y0, n * 8)); CK(hipMalloc(&d_y1, n * 8));
+    CK(hipMemcpy(d_len, len.data(), n * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_width, width.data(), n_slices * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_wcol, wcol.data(), wcol.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_wsize, wsize.data(), n_blocks * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_ptr, ptr.data(), (n_slices + 1) * 8, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_pptr, pptr.data(), (n_slices + 1) * 8, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_vptr, vptr.data(), (n_slices + 1) * 8, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_lo, lidx_o.data(), e_old * 2, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_ln, lidx_n.data(), pe_new * 2, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_col_o, col_o.data(), col_o.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_col_n, col_n.data(), col_n.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_vo, val_o.data(), e_old * 8, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_vn, val_n.data(), ve_new * 8, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_x, xh.data(), n * 8, hipMemcpyHostToDevice));
+    Mat Ao = A, An = A;
+    Ao.len = An.len = d_len; Ao.width = An.width = d_width; Ao.wcol = An.wcol = d_wcol; Ao.wsize = An.wsize = d_wsize;
+    Ao.ptr = d_ptr; Ao.lidx = d_lo; Ao.col = d_col_o; Ao.val = d_vo;
+    An.pptr = d_pptr; An.vptr = d_vptr; An.lidx = d_ln; An.col = d_col_n; An.val = d_vn;
+
+    const unsigned grid = (unsigned)n_blocks;  // one workgroup per block, as launch_spmv
+    const size_t smem = global ? 0 : (size_t)ws * 8;
+    auto launch = [&](int which) {
+        if (which == 0) {
+            if (global) hipLaunchKernelGGL(depth_major_k<true>, dim3(grid), dim3(256), smem, 0, Ao, d_x, d_y0);
+            else hipLaunchKernelGGL(depth_major_k<false>, dim3(grid), dim3(256), smem, 0, Ao, d_x, d_y0);
+        } else {
+            if (global) hipLaunchKernelGGL(chunked_k<true>, dim3(grid), dim3(256), smem, 0, An, d_x, d_y1);
+            else hipLaunchKernelGGL(chunked_k<false>, dim3(grid), dim3(256), smem, 0, An, d_x, d_y1);
+        }
+    };
+    launch(0); launch(1);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    std::vector<double> y0(n), y1(n);
+    CK(hipMemcpy(y0.data(), d_y0, n * 8, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(y1.data(), d_y1, n * 8, hipMemcpyDeviceToHost));
+    int64_t diff = 0;
+    for (int64_t r = 0; r < n; ++r) diff += memcmp(&y0[r], &y1[r], 8) != 0;
+    // a CPU check of a few rows (the same ascending sum, fused as the device compiles it)
+    int64_t cpu_bad = 0;
+    for (int64_t r = 0; r < n; r += 9973) {
+        double acc = 0.;
+        for (int k = 0; k < len[r]; ++k) acc = std::fma(val_of(r, k), global ? xh[col_of(r, k)] : xh[wcol[(r / 256) * ws + pos_of(r, k)]], acc);  // (the device contracts)
+        cpu_bad += memcmp(&acc, &y0[r], 8) != 0;
+    }
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    std::vector<float> t[2];
+    for (int i = 0; i < reps; ++i)
+        for (int w = 0; w < 2; ++w) {
+            CK(hipEventRecord(e0, 0)); launch(w); CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1)); t[w].push_back(ms * 1e3f);
+        }
+    const double bytes_o = (double)e_old * (global ? 12 : 10), bytes_n = (double)pe_new * (global ? 0 : 2) + (double)ve_new * (global ? 12 : 8);
+    const double alg = (double)nnz * (global ? 12 : 10) + (double)n * 8 + (global ? 0 : (double)n_blocks * ws * 12);
+    printf("rows %lld, entries %lld (%.1f per row), %s, window %d\n", (long long)n, (long long)nnz, (double)nnz / n, global ? "global gathers" : "LDS window", ws);
+    printf("stream bytes: depth-major %.1f MB, chunked %.1f MB (%+.2f %%)\n", bytes_o / 1e6, bytes_n / 1e6, 100. * (bytes_n / bytes_o - 1.));
+    printf("y bit-identical: %s (%lld rows differ), CPU check %lld bad\n", diff == 0 ? "yes" : "NO", (long long)diff, (long long)cpu_bad);
+    const char *names[2] = {"depth-major", "chunked"};
+    double med[2];
+    for (int w = 0; w < 2; ++w) {
+        std::sort(t[w].begin(), t[w].end());
+        med[w] = t[w][t[w].size() / 2];
+        printf("%-12s median %8.1f us  min %8.1f us  %.2f TB/s of algorithmic bytes (%.3f of 8 TB/s)\n", names[w], med[w], (double)t[w][0], alg / med[w] / 1e6,
+               alg / med[w] / 8e6);
+    }
+    printf("chunked / depth-major: %.3f\n", med[1] / med[0]);
+    return diff != 0;
+}
