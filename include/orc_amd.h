@@ -305,6 +305,29 @@ int orc_solver_restore(OrcSolver *s);
 int orc_solver_assemble_momentum(OrcSolver *s, double *a_u, double *a_v, double *a_w, double *b_u, double *b_v, double *b_w, double peclet[3]);
 int orc_solver_assemble_pressure(OrcSolver *s, double *a_p, double *b_p);
 
+/* ---------- implicit time stepping (new-build extension, orc_types.h OrcTransient) ----------
+ * Off by default: a solver that never calls orc_solver_set_transient runs exactly the steady code paths.
+ *  - orc_solver_set_transient(s, t): t == NULL switches back to steady SIMPLE; otherwise validates t and turns the arm on
+ *    with 0 known time levels.  Invalid (dt <= 0 or non-finite, unknown scheme, inner_iterations == 0, negative or NaN
+ *    inner_tolerance, reserved0 != 0, or a solver with frozen_diagonals = 0) is ORC_ERR_BAD_ARGUMENT, solver unchanged.
+ *  - while the arm is on and at least one level is known, every momentum assembly (orc_solver_iterate,
+ *    orc_solver_assemble_momentum and the pressure system through the diagonals) carries the time term; BDF2 runs as Euler
+ *    while only one level is known.  orc_solver_iterate does not shift the levels.
+ *  - orc_solver_set_time_levels: levels n (and n-1, or NULL for one known level) in ORC cell order; needs the arm on.
+ *  - orc_solver_advance: per time step, n-1 <- n, n <- current fields (known levels min(k + 1, 2)), then up to
+ *    inner_iterations SIMPLE iterations, fewer once both correction norms (report slots 6, 7) are below inner_tolerance times
+ *    their values at the first inner iteration.  report (may be NULL): 10 doubles per step, the 8 of orc_solver_iterate for
+ *    the last inner iteration, the inner iterations used, and the time reached since the arm was enabled.
+ *  - orc_solver_snapshot / orc_solver_restore include the time levels, their count and the time while the arm is on. */
+int orc_solver_set_transient(OrcSolver *s, const OrcTransient *t);
+int orc_solver_set_time_levels(OrcSolver *s, const double *u_n, const double *v_n, const double *w_n, const double *u_nm1,
+                               const double *v_nm1, const double *w_nm1);
+int orc_solver_advance(OrcSolver *s, uint64_t time_steps, double *report);
+/* solve_steady's counterpart: time_steps steps of t from u, v, w, p (updated in place); report_cb every reporting_interval
+ * steps with the last inner iteration's report (iteration = time step, ms_per_iter = ms per time step) */
+int orc_solve_transient(OrcMesh *m, double *u, double *v, double *w, double *p, const OrcSettings *settings, double rho, double mu,
+                        const OrcTransient *t, uint64_t time_steps, uint64_t reporting_interval, OrcReportFn report_cb, void *user);
+
 /* ---------- measurement hooks (bench.py): HIP-event timed launches of single kernels ---------- */
 /* y = A x with the momentum matrix a_u of the solver, `reps` launches; returns average ms per launch */
 int orc_bench_spmv(OrcSolver *s, int reps, double *avg_ms, double *checksum);

@@ -153,6 +153,19 @@ typedef struct OrcSettings {
                                         anything else is ORC_ERR_BAD_ARGUMENT when the GMRES arm runs */
 } OrcSettings;
 
+/* Implicit time stepping (new-build extension; ORC's roadmap lists "Iterate transient" as not done).  With c = rho V_P / dt
+ * the three momentum systems get  Euler: diag += c, b += c u_n;  BDF2: diag += 1.5 c, b += c (2 u_n - 0.5 u_nm1).
+ * orc_amd.h: orc_solver_set_transient, orc_solver_advance, orc_solve_transient. */
+enum OrcTimeScheme { ORC_TIME_EULER = 0, ORC_TIME_BDF2 = 1 };
+
+typedef struct OrcTransient {
+    double dt;                 /* > 0, finite */
+    int32_t scheme;            /* OrcTimeScheme */
+    int32_t reserved0;         /* 0 */
+    uint64_t inner_iterations; /* >= 1: SIMPLE iterations per time step at most */
+    double inner_tolerance;    /* >= 0; 0 = always inner_iterations */
+} OrcTransient;
+
 #ifdef __cplusplus
 }
 #endif

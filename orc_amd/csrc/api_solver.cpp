@@ -1,6 +1,7 @@
 // api_solver.cpp — C ABI for mesh::Mesh, discretization::* and solver::solve_steady.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <memory>
 
 #include "assembly.hpp"
@@ -255,6 +256,15 @@ int orc_solver_snapshot(OrcSolver *s) {
         ORC_TRY(t.snap[k].ensure((size_t)t.n));
         ORC_TRY(vec_copy(t.snap[k].p, src[k]->p, t.n));
     }
+    t.snap_transient = t.transient;
+    if (t.transient) {  // the time levels of the step in progress (bench.py never enables the arm: its snapshots are unchanged)
+        for (int k = 0; k < 6; ++k) {
+            ORC_TRY(t.snap_lev[k].ensure((size_t)t.n));
+            ORC_TRY(vec_copy(t.snap_lev[k].p, t.lev[k].p, t.n));
+        }
+        t.snap_time_levels = t.time_levels;
+        t.snap_time = t.time;
+    }
     t.snap_iterations = t.iterations_done;
     t.has_snapshot = true;
     return ORC_OK;
@@ -266,6 +276,11 @@ int orc_solver_restore(OrcSolver *s) {
     if (!t.has_snapshot) return set_error(ORC_ERR_BAD_ARGUMENT, "orc_solver_restore without orc_solver_snapshot");
     DevBuf<double> *dst[7] = {&t.u, &t.v, &t.w, &t.p, &t.du, &t.dv, &t.dw};
     for (int k = 0; k < 7; ++k) ORC_TRY(vec_copy(dst[k]->p, t.snap[k].p, t.n));  // asynchronous, library stream
+    if (t.snap_transient && t.transient) {
+        for (int k = 0; k < 6; ++k) ORC_TRY(vec_copy(t.lev[k].p, t.snap_lev[k].p, t.n));
+        t.time_levels = t.snap_time_levels;
+        t.time = t.snap_time;
+    }
     t.iterations_done = t.snap_iterations;
     return ORC_OK;
 }
@@ -300,6 +315,116 @@ int orc_solver_assemble_pressure(OrcSolver *s, double *a_p, double *b_p) {
     if (a_p) ORC_TRY(download_csr_values(*t.mesh, t.a_p, a_p, tmp));
     if (b_p) ORC_TRY(t.b_p.download(b_p, (size_t)t.n));
     return fetch_status(t);
+}
+
+// ---------------------------------------------------------------- implicit time stepping (OrcTransient)
+int orc_solver_set_transient(OrcSolver *s, const OrcTransient *t) {
+    if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
+    SolverState &st = s->st;
+    if (!t) {  // back to steady SIMPLE: k_momentum launches nothing new from here on
+        st.transient = false;
+        st.time_levels = 0;
+        return ORC_OK;
+    }
+    if (!(t->dt > 0.) || !std::isfinite(t->dt)) return set_error(ORC_ERR_BAD_ARGUMENT, "transient: dt must be positive and finite");
+    if (t->scheme != ORC_TIME_EULER && t->scheme != ORC_TIME_BDF2) return set_error(ORC_ERR_BAD_ARGUMENT, "transient: unknown time scheme %d", t->scheme);
+    if (t->reserved0 != 0) return set_error(ORC_ERR_BAD_ARGUMENT, "transient: reserved0 must be 0");
+    if (t->inner_iterations == 0) return set_error(ORC_ERR_BAD_ARGUMENT, "transient: inner_iterations must be at least 1");
+    if (!(t->inner_tolerance >= 0.)) return set_error(ORC_ERR_BAD_ARGUMENT, "transient: inner_tolerance must be >= 0");
+    // the in-place diagonal reads of frozen_diagonals = 0 would see this iteration's diagonals without the time term
+    if (st.settings.frozen_diagonals == 0) return set_error(ORC_ERR_BAD_ARGUMENT, "transient: not available with frozen_diagonals = 0");
+    for (auto &b : st.lev) ORC_TRY(b.ensure((size_t)std::max<int64_t>(st.n, 1)));
+    st.tr = *t;
+    st.transient = true;
+    st.time_levels = 0;
+    st.time = 0.;
+    return ORC_OK;
+}
+
+int orc_solver_set_time_levels(OrcSolver *s, const double *u_n, const double *v_n, const double *w_n, const double *u_nm1,
+                               const double *v_nm1, const double *w_nm1) {
+    if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
+    SolverState &st = s->st;
+    if (!st.transient) return set_error(ORC_ERR_BAD_ARGUMENT, "time levels without orc_solver_set_transient");
+    if (!u_n || !v_n || !w_n) return set_error(ORC_ERR_BAD_ARGUMENT, "level n must be given");
+    const int given = (u_nm1 != nullptr) + (v_nm1 != nullptr) + (w_nm1 != nullptr);
+    if (given != 0 && given != 3) return set_error(ORC_ERR_BAD_ARGUMENT, "level n-1: all of u, v, w or none");
+    const size_t n = (size_t)st.n;
+    const std::vector<int64_t> &g = st.mesh->h_global_ids;
+    const double *src[6] = {u_n, v_n, w_n, u_nm1, v_nm1, w_nm1};
+    std::vector<double> tmp;
+    for (int k = 0; k < (given ? 6 : 3); ++k) {
+        if (g.empty()) { ORC_TRY(st.lev[k].upload(src[k], n)); continue; }
+        tmp.resize(n);
+        for (size_t c = 0; c < n; ++c) tmp[c] = src[k][g[c]];
+        ORC_TRY(st.lev[k].upload(tmp.data(), n));
+    }
+    st.time_levels = given ? 2 : 1;
+    return ORC_OK;
+}
+
+namespace {
+// one time step: shift the levels (n-1 <- n, n <- current fields), then up to inner_iterations SIMPLE iterations
+int advance_one(SolverState &st, double *row /*10*/) {
+    if (st.time_levels >= 1)
+        for (int k = 0; k < 3; ++k) ORC_TRY(vec_copy(st.lev[3 + k].p, st.lev[k].p, st.n));
+    const double *cur[3] = {st.u.p, st.v.p, st.w.p};
+    for (int k = 0; k < 3; ++k) ORC_TRY(vec_copy(st.lev[k].p, cur[k], st.n));
+    st.time_levels = std::min(st.time_levels + 1, 2);
+    st.time += st.tr.dt;
+    const double tol = st.tr.inner_tolerance;
+    double rep[8] = {0., 0., 0., 0., 0., 0., 0., 0.}, first_vc = 0., first_pc = 0.;
+    uint64_t used = 0;
+    for (uint64_t it = 0; it < st.tr.inner_iterations; ++it) {
+        ORC_TRY(solver_iterate(st, 1, rep));
+        ++used;
+        if (it == 0) { first_vc = rep[6]; first_pc = rep[7]; }
+        if (tol > 0. && (rep[6] < tol * first_vc || rep[6] == 0.) && (rep[7] < tol * first_pc || rep[7] == 0.)) break;
+    }
+    if (row) {
+        std::copy(rep, rep + 8, row);
+        row[8] = (double)used;
+        row[9] = st.time;
+    }
+    return ORC_OK;
+}
+}  // namespace
+
+int orc_solver_advance(OrcSolver *s, uint64_t time_steps, double *report) {
+    if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
+    if (!s->st.transient) return set_error(ORC_ERR_BAD_ARGUMENT, "orc_solver_advance without orc_solver_set_transient");
+    GuardNote note;
+    int st = ORC_OK;
+    for (uint64_t k = 0; k < time_steps && st == ORC_OK; ++k) st = advance_one(s->st, report ? report + 10 * k : nullptr);
+    note.leave(st);
+    return st;
+}
+
+int orc_solve_transient(OrcMesh *m, double *u, double *v, double *w, double *p, const OrcSettings *settings, double rho, double mu,
+                        const OrcTransient *t, uint64_t time_steps, uint64_t reporting_interval, OrcReportFn report_cb, void *user) {
+    if (!m || !settings || !t || !u || !v || !w || !p) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
+    int st = ORC_OK;
+    OrcSolver *s = orc_solver_create(m, settings, rho, mu, &st);
+    if (!s) return st;
+    std::unique_ptr<OrcSolver> guard(s);
+    ORC_TRY(orc_solver_set_transient(s, t));
+    ORC_TRY(orc_solver_set_fields(s, u, v, w, p));
+    GuardNote note;
+    auto start = std::chrono::steady_clock::now();
+    for (uint64_t k = 1; k <= time_steps && st == ORC_OK; ++k) {
+        double row[10];
+        st = advance_one(s->st, row);
+        if (report_cb && reporting_interval > 0 && k % reporting_interval == 0 && st == ORC_OK) {
+            auto now = std::chrono::steady_clock::now();
+            double ms = std::chrono::duration<double, std::milli>(now - start).count() / (double)reporting_interval;
+            start = now;
+            report_cb(k, row, row + 3, row[6], row[7], ms, user);
+        }
+    }
+    if (st == ORC_OK) st = post_loop_gradients_dev(s->st);
+    int st2 = orc_solver_get_fields(s, u, v, w, p);
+    note.leave(st != ORC_OK ? st : st2);
+    return st != ORC_OK ? st : st2;
 }
 
 // ---------------------------------------------------------------- discretization::* with host arrays

@@ -719,6 +719,43 @@ __global__ __launch_bounds__(kBlock) void peclet_stats_k(const double *__restric
     }
 }
 
+// ------------------------------------------------------------------ implicit time term (transient arm)
+// After momentum_k, per owned cell with c = rho V_P / dt:  Euler  diag += c,     b += c u_n;
+//                                                          BDF2   diag += 1.5 c, b += c (2 u_n - 0.5 u_nm1).
+// The new diagonal also goes to du/dv/dw (written, never read), so Rhie-Chow and the p' coefficients see the time term.
+// One pass over the three systems; the diagonal slots sit at depth k of their 64-row slice (SellDev::diag_pos), so a wave's
+// read-modify-writes fall into as many 512-byte segments as its rows have distinct diagonal depths.
+struct TimeTermArgs {
+    const double *un, *vn, *wn, *unm1, *vnm1, *wnm1;
+    double *a_u, *a_v, *a_w, *b_u, *b_v, *b_w, *du, *dv, *dw;
+    double rho, dt;
+};
+
+template <bool kBdf2>
+__global__ __launch_bounds__(kBlock) void time_term_k(int64_t n_own, const double *__restrict__ vol, const int32_t *__restrict__ diag_pos,
+                                                      TimeTermArgs T) {
+    GRID_STRIDE(c, n_own) {
+        const double coef = (T.rho * vol[c]) / T.dt;
+        const int dpos = diag_pos[c];
+        double add, su, sv, sw;
+        if (kBdf2) {
+            add = 1.5 * coef;
+            su = coef * (2.0 * T.un[c] - 0.5 * T.unm1[c]);
+            sv = coef * (2.0 * T.vn[c] - 0.5 * T.vnm1[c]);
+            sw = coef * (2.0 * T.wn[c] - 0.5 * T.wnm1[c]);
+        } else {
+            add = coef;
+            su = coef * T.un[c];
+            sv = coef * T.vn[c];
+            sw = coef * T.wn[c];
+        }
+        const double d_u = T.a_u[dpos] + add, d_v = T.a_v[dpos] + add, d_w = T.a_w[dpos] + add;
+        T.a_u[dpos] = d_u; T.a_v[dpos] = d_v; T.a_w[dpos] = d_w;
+        T.du[c] = d_u; T.dv[c] = d_v; T.dw[c] = d_w;
+        T.b_u[c] += su; T.b_v[c] += sv; T.b_w[c] += sw;
+    }
+}
+
 // ------------------------------------------------------------------ K12: pressure-correction system
 // discretization.rs:359-448 with the fixed pattern (no COO build / sort per iteration)
 __global__ void pressure_k(MeshDev M, SellDev P, const double *__restrict__ flux, const double *__restrict__ coef, double rho,
@@ -1080,6 +1117,7 @@ int k_momentum(SolverState &s, double *peclet_host) {
     hipLaunchKernelGGL(reduce_minmax_k, dim3(1), dim3(64), 0, ctx().stream, s.partials.p, g, s.scal.p + 8);
     ORC_HIP(hipGetLastError());
     if (ref_pe) ORC_TRY(sum_reference(s.pe.p, s.n, s.scal.p + 8));
+    if (s.transient && s.time_levels > 0) ORC_TRY(k_time_term(s));  // after the Peclet statistics, which exclude the time term
     if (peclet_host) {
         if (s.mesh->halo.active()) {  // statistics over the whole mesh: sum; max of (-min, max)
             hipLaunchKernelGGL(negate_k, dim3(1), dim3(1), 0, ctx().stream, s.scal.p + 9);
@@ -1091,6 +1129,20 @@ int k_momentum(SolverState &s, double *peclet_host) {
         ORC_HIP(hipStreamSynchronize(ctx().stream));
         peclet_host[0] /= (double)s.mesh->n_global;  // discretization.rs:355
     }
+    return ORC_OK;
+}
+
+int k_time_term(SolverState &s) {
+    OrcMesh &m = *s.mesh;
+    const bool bdf2 = s.tr.scheme == ORC_TIME_BDF2 && s.time_levels >= 2;  // BDF2 starts as Euler while one level is known
+    TimeTermArgs T{s.lev[0].p, s.lev[1].p, s.lev[2].p, s.lev[3].p, s.lev[4].p, s.lev[5].p, s.a_u.p, s.a_v.p, s.a_w.p,
+                   s.b_u.p, s.b_v.p, s.b_w.p, s.du.p, s.dv.p, s.dw.p, s.rho, s.tr.dt};
+    const int g = grid_for(s.n_own);
+    if (bdf2)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(time_term_k<true>), dim3(g), dim3(kBlock), 0, ctx().stream, s.n_own, m.vol.p, m.pat.diag_pos.p, T);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(time_term_k<false>), dim3(g), dim3(kBlock), 0, ctx().stream, s.n_own, m.vol.p, m.pat.diag_pos.p, T);
+    ORC_HIP(hipGetLastError());
     return ORC_OK;
 }
 

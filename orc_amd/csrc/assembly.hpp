@@ -111,6 +111,17 @@ struct SolverState {
     DevBuf<double> snap[7];
     uint64_t snap_iterations = 0;
     bool has_snapshot = false;
+    // Implicit time stepping (orc_solver_set_transient): off unless enabled.  lev[0..2] = u, v, w at level n, lev[3..5] at n-1,
+    // allocated on first enabling; time_term_k adds the time term at the end of k_momentum while transient && time_levels > 0.
+    bool transient = false;
+    OrcTransient tr{};
+    int time_levels = 0;  // known previous levels, 0..2
+    double time = 0.;     // time reached since the arm was enabled
+    DevBuf<double> lev[6];
+    DevBuf<double> snap_lev[6];
+    int snap_time_levels = 0;
+    double snap_time = 0.;
+    bool snap_transient = false;
 };
 
 int mesh_upload(OrcMesh &m, int64_t n_own, int64_t n_cells, int64_t n_faces, int32_t n_zones, const int64_t *face_c0, const int64_t *face_c1,
@@ -125,6 +136,7 @@ int k_init_momentum(SolverState &s);             // discretization.rs:450-472
 int k_gradients(SolverState &s, bool need_gu);   // K9   solver.rs:774-802, 874-902
 int k_face_flux(SolverState &s, bool with_pf);   // K10  solver.rs:1007-1150
 int k_momentum(SolverState &s, double *peclet_host /*3, may be null*/);  // K11  discretization.rs:134-356
+int k_time_term(SolverState &s);                 // implicit time term on the momentum systems (transient arm, k_momentum)
 int k_pressure_correction(SolverState &s);       // K12  discretization.rs:359-448
 int k_apply_correction(SolverState &s, double *sums_host /*5: p'^2, |dU|^2, sum u, sum v, sum w*/);  // K13 solver.rs:1170-1227
 int solver_iterate(SolverState &s, uint64_t iterations, double *report);

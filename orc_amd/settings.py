@@ -56,3 +56,19 @@ class PreconditionMethod:  # lib.rs:181-185
 
 class FaceConditionTypes:  # mesh.rs:25-65
     Interior, Wall, PressureInlet, PressureOutlet, Symmetry, VelocityInlet = 2, 3, 4, 5, 7, 10
+
+
+class TimeScheme:  # include/orc_types.h OrcTimeScheme
+    Euler, BDF2 = 0, 1
+
+
+class Transient(C.Structure):
+    """OrcTransient: implicit time stepping with a fixed step (Solver.set_transient, solve_transient)."""
+    _fields_ = [
+        ("dt", C.c_double), ("scheme", C.c_int32), ("reserved0", C.c_int32),
+        ("inner_iterations", C.c_uint64), ("inner_tolerance", C.c_double),
+    ]
+
+    @classmethod
+    def make(cls, dt, scheme=TimeScheme.Euler, inner_iterations=20, inner_tolerance=0.0):
+        return cls(dt=dt, scheme=scheme, reserved0=0, inner_iterations=inner_iterations, inner_tolerance=inner_tolerance)

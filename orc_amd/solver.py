@@ -36,6 +36,26 @@ def solve_steady(mesh, u, v, w, p, numerical_settings, rho, mu, iteration_count,
     return st
 
 
+def solve_transient(mesh, u, v, w, p, settings, rho, mu, transient, time_steps, reporting_interval=0, report=None,
+                    raise_on_error=True):
+    """Implicit time stepping (orc_solve_transient): time_steps steps of `transient` (settings.Transient) from u, v, w, p,
+    updated in place.  report(step, mean_velocity[3], peclet[3], velocity_correction, pressure_correction, ms_per_step)
+    with the last inner iteration's values."""
+    for a in (u, v, w, p):
+        assert a.dtype == np.float64 and a.flags.c_contiguous and len(a) == mesh.n_cells
+    cb = None
+    if report is not None:
+        def _cb(it, mv, pe, vc, pc, ms, _user):
+            report(it, (mv[0], mv[1], mv[2]), (pe[0], pe[1], pe[2]), vc, pc, ms)
+        cb = _REPORT_FN(_cb)
+    st = lib().orc_solve_transient(mesh.ptr, _p(u), _p(v), _p(w), _p(p), C.byref(settings), C.c_double(rho), C.c_double(mu),
+                                   C.byref(transient), C.c_uint64(time_steps), C.c_uint64(reporting_interval),
+                                   cb if cb is not None else C.cast(None, _REPORT_FN), None)
+    if raise_on_error:
+        check(st)
+    return st
+
+
 def calculate_gradients(mesh, u, v, w, p, settings, velocity=True):
     """Green-Gauss arms of calculate_pressure_gradient / calculate_velocity_gradient for every cell."""
     n = mesh.n_cells
@@ -77,6 +97,32 @@ class Solver:
         st = lib().orc_solver_iterate(self.ptr, C.c_uint64(iterations), _p(rep) if report else None)
         if raise_on_error:
             check(st)
+        return (st, rep) if report else st
+
+    def set_transient(self, transient=None, raise_on_error=True):
+        """orc_solver_set_transient: a settings.Transient turns implicit time stepping on (0 known levels), None turns it off"""
+        st = lib().orc_solver_set_transient(self.ptr, C.byref(transient) if transient is not None else None)
+        if raise_on_error:
+            check(st)
+        return st
+
+    def set_time_levels(self, u_n, v_n, w_n, u_nm1=None, v_nm1=None, w_nm1=None, raise_on_error=True):
+        """orc_solver_set_time_levels: the previous time levels of the step in progress, ORC cell order (n-1 optional)"""
+        lv = [_f64(a) for a in (u_n, v_n, w_n)]
+        old = [None if a is None else _f64(a) for a in (u_nm1, v_nm1, w_nm1)]
+        st = lib().orc_solver_set_time_levels(self.ptr, *[_p(a) for a in lv], *[None if a is None else _p(a) for a in old])
+        if raise_on_error:
+            check(st)
+        return st
+
+    def advance(self, steps=1, report=False, raise_on_error=True):
+        """orc_solver_advance: `steps` time steps.  report=True returns an array (steps, 10): the 8 values of iterate() for the
+        last inner iteration, the inner iterations used, and the time reached (with raise_on_error=False: (status, array))."""
+        rep = np.zeros((steps, 10)) if report else None
+        st = lib().orc_solver_advance(self.ptr, C.c_uint64(steps), _p(rep) if report else None)
+        if raise_on_error:
+            check(st)
+            return rep if report else st
         return (st, rep) if report else st
 
     def assemble_momentum(self):
