@@ -328,6 +328,40 @@ int orc_solver_advance(OrcSolver *s, uint64_t time_steps, double *report);
 int orc_solve_transient(OrcMesh *m, double *u, double *v, double *w, double *p, const OrcSettings *settings, double rho, double mu,
                         const OrcTransient *t, uint64_t time_steps, uint64_t reporting_interval, OrcReportFn report_cb, void *user);
 
+/* ---------- passive scalar transport (new-build extension, orc_types.h OrcScalarSettings) ----------
+ * Off by default: a solver that never calls orc_solver_set_scalar runs exactly the code it ran before.  The scalar is carried
+ * by the flux face_k forms from the current u, v, w, p (Rhie-Chow included) and changes no bit of the flow state.
+ *  - orc_scalar_settings_default: UD, BiCGSTAB + Jacobi, 500 iterations, relative threshold 1e-10, relaxation 0.5,
+ *    30 outer rounds / 1e-8, Gamma = 1e-3.
+ *  - orc_solver_set_scalar(s, c): c == NULL turns the arm off and frees its buffers; otherwise validates c (Gamma <= 0 or
+ *    non-finite, unknown solver or preconditioner, reserved0 != 0, iterations or outer_iterations 0, negative tolerances:
+ *    ORC_ERR_BAD_ARGUMENT; CD2 or an unknown scheme: ORC_ERR_UNSUPPORTED_SCHEME) and turns the arm on with phi = 0, no
+ *    source, no time levels and every zone DEFAULT.  A refusal leaves the solver unchanged.
+ *  - orc_solver_set_scalar_bc: zone = the index orc_mesh_update_zones uses; kind an OrcScalarBc; interior zones refused.
+ *  - fields, sources and levels in ORC cell order.  orc_solver_set_scalar_levels needs both arms on (phi_nm1 may be NULL).
+ *  - orc_solver_solve_scalar: one solve (UD, CD1: one linear solve; TVD: up to outer_iterations rounds of gradient, face
+ *    correction, assembly and linear solve).  With Rhie-Chow it needs momentum diagonals (an orc_solver_iterate or an
+ *    assembly first): ORC_ERR_BAD_ARGUMENT otherwise.  report (may be NULL): rounds used, last relative change, min phi,
+ *    max phi over the owned cells.  orc_solver_iterate never touches the scalar.
+ *  - orc_solver_advance with both arms on: after each step's SIMPLE iterations the scalar levels shift (n-1 <- n, n <- phi)
+ *    and the scalar is solved once with its time term; orc_solver_last_scalar_report returns that solve's report.
+ *  - orc_solver_assemble_scalar: the system of the current state (TVD: its correction from the current phi); a in pattern
+ *    order like orc_solver_assemble_momentum, b in the mesh's internal cell order; either may be NULL.
+ *  - orc_solver_scalar_boundary_flux: per zone (n_zones doubles) the convective plus diffusive flux of phi INTO the domain
+ *    under the current phi and flow; interior zones 0.
+ *  - orc_solver_snapshot / orc_solver_restore include phi, its levels and their count while the arm is on. */
+void orc_scalar_settings_default(OrcScalarSettings *c);
+int orc_solver_set_scalar(OrcSolver *s, const OrcScalarSettings *c);
+int orc_solver_set_scalar_bc(OrcSolver *s, int32_t zone, int32_t kind, double value);
+int orc_solver_set_scalar_field(OrcSolver *s, const double *phi);
+int orc_solver_get_scalar_field(OrcSolver *s, double *phi);
+int orc_solver_set_scalar_source(OrcSolver *s, const double *source /* per unit volume, NULL = none */);
+int orc_solver_set_scalar_levels(OrcSolver *s, const double *phi_n, const double *phi_nm1 /* may be NULL */);
+int orc_solver_solve_scalar(OrcSolver *s, double report[4]);
+int orc_solver_last_scalar_report(OrcSolver *s, double report[4]);
+int orc_solver_assemble_scalar(OrcSolver *s, double *a, double *b);
+int orc_solver_scalar_boundary_flux(OrcSolver *s, double *per_zone);
+
 /* ---------- measurement hooks (bench.py): HIP-event timed launches of single kernels ---------- */
 /* y = A x with the momentum matrix a_u of the solver, `reps` launches; returns average ms per launch */
 int orc_bench_spmv(OrcSolver *s, int reps, double *avg_ms, double *checksum);

@@ -166,6 +166,32 @@ typedef struct OrcTransient {
     double inner_tolerance;    /* >= 0; 0 = always inner_iterations */
 } OrcTransient;
 
+/* Passive scalar transport (new-build extension; ORC has no scalar equation):
+ *     rho dphi/dt + div(rho U phi) = div(Gamma grad phi) + S
+ * carried by the solver's current flow, which it never changes.  orc_amd.h: orc_solver_set_scalar and its companions;
+ * DESIGN.md "Passive scalar transport" defines the discretisation.  A zone's scalar condition: */
+enum OrcScalarBc {
+    ORC_SCALAR_BC_DEFAULT = 0,       /* from the flow's zone type: Wall, Symmetry -> FLUX 0; VelocityInlet, PressureInlet -> VALUE 0;
+                                        PressureOutlet -> ZERO_GRADIENT */
+    ORC_SCALAR_BC_VALUE = 1,         /* phi_b = value */
+    ORC_SCALAR_BC_FLUX = 2,          /* value = diffusive flux INTO the domain per unit area */
+    ORC_SCALAR_BC_ZERO_GRADIENT = 3  /* FLUX 0 */
+};
+
+typedef struct OrcScalarSettings {
+    double diffusivity;                    /* Gamma > 0, finite, in the units of mu; default 1e-3 */
+    int32_t scheme;                        /* OrcMomentumDiscretization except CD2; default UD.  TVD_* = implicit UD + deferred
+                                              correction with the momentum scheme's limiter, iterated by the outer (Picard) loop */
+    int32_t solver_type;                   /* OrcSolutionMethod; default BiCGSTAB */
+    int32_t preconditioner;                /* OrcPreconditionMethod; default Jacobi */
+    int32_t reserved0;                     /* 0 */
+    uint64_t iterations;                   /* >= 1: linear solver iterations; default 500 */
+    double relative_convergence_threshold; /* >= 0; default 1e-10 */
+    double relaxation;                     /* the linear solver's relaxation factor (as OrcSettings.relaxation); default 0.5 */
+    uint64_t outer_iterations;             /* >= 1: Picard rounds of a TVD solve at most; default 30 */
+    double outer_tolerance;                /* >= 0: stop once |phi_new - phi_old|_2 <= outer_tolerance |phi_new|_2; default 1e-8 */
+} OrcScalarSettings;
+
 #ifdef __cplusplus
 }
 #endif

@@ -265,6 +265,17 @@ int orc_solver_snapshot(OrcSolver *s) {
         t.snap_time_levels = t.time_levels;
         t.snap_time = t.time;
     }
+    t.sc.snap_on = t.sc.on;
+    if (t.sc.on) {  // the scalar, its levels and their count (orc_solver_set_scalar)
+        const size_t n = (size_t)std::max<int64_t>(t.n, 1);
+        ORC_TRY(t.sc.snap_phi.ensure(n));
+        ORC_TRY(vec_copy(t.sc.snap_phi.p, t.sc.phi.p, t.n));
+        for (int k = 0; k < 2; ++k) {
+            ORC_TRY(t.sc.snap_lev[k].ensure(n));
+            ORC_TRY(vec_copy(t.sc.snap_lev[k].p, t.sc.lev[k].p, t.n));
+        }
+        t.sc.snap_levels = t.sc.levels;
+    }
     t.snap_iterations = t.iterations_done;
     t.has_snapshot = true;
     return ORC_OK;
@@ -280,6 +291,11 @@ int orc_solver_restore(OrcSolver *s) {
         for (int k = 0; k < 6; ++k) ORC_TRY(vec_copy(t.lev[k].p, t.snap_lev[k].p, t.n));
         t.time_levels = t.snap_time_levels;
         t.time = t.snap_time;
+    }
+    if (t.sc.snap_on && t.sc.on) {
+        ORC_TRY(vec_copy(t.sc.phi.p, t.sc.snap_phi.p, t.n));
+        for (int k = 0; k < 2; ++k) ORC_TRY(vec_copy(t.sc.lev[k].p, t.sc.snap_lev[k].p, t.n));
+        t.sc.levels = t.sc.snap_levels;
     }
     t.iterations_done = t.snap_iterations;
     return ORC_OK;
@@ -324,6 +340,7 @@ int orc_solver_set_transient(OrcSolver *s, const OrcTransient *t) {
     if (!t) {  // back to steady SIMPLE: k_momentum launches nothing new from here on
         st.transient = false;
         st.time_levels = 0;
+        st.sc.levels = 0;
         return ORC_OK;
     }
     if (!(t->dt > 0.) || !std::isfinite(t->dt)) return set_error(ORC_ERR_BAD_ARGUMENT, "transient: dt must be positive and finite");
@@ -337,6 +354,7 @@ int orc_solver_set_transient(OrcSolver *s, const OrcTransient *t) {
     st.tr = *t;
     st.transient = true;
     st.time_levels = 0;
+    st.sc.levels = 0;
     st.time = 0.;
     return ORC_OK;
 }
@@ -381,6 +399,7 @@ int advance_one(SolverState &st, double *row /*10*/) {
         if (it == 0) { first_vc = rep[6]; first_pc = rep[7]; }
         if (tol > 0. && (rep[6] < tol * first_vc || rep[6] == 0.) && (rep[7] < tol * first_pc || rep[7] == 0.)) break;
     }
+    ORC_TRY(scalar_step_dev(st));  // scalar arm on: its levels shift and it is solved once on this step's flow
     if (row) {
         std::copy(rep, rep + 8, row);
         row[8] = (double)used;

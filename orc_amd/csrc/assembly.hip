@@ -540,22 +540,7 @@ __global__ void face_coef_k(MeshDev M, const double *__restrict__ du, const doub
 }
 
 // ------------------------------------------------------------------ K11: momentum matrices
-__device__ __forceinline__ double psi_eval(int momentum, double r) {  // lib.rs:107-118
-    switch (momentum) {
-    case ORC_MOMENTUM_TVD_UD: return 0.;
-    case ORC_MOMENTUM_TVD_CD1: return 1.;
-    case ORC_MOMENTUM_TVD_LUD: return r;
-    case ORC_MOMENTUM_TVD_QUICK: return (3. + r) / 4.;
-    default: {  // UMIST; f64::min / max ignore NaN like fmin / fmax
-        double acc = INFINITY;
-        acc = fmin(acc, 2. * r);
-        acc = fmin(acc, (1. + 3. * r) / 4.);
-        acc = fmin(acc, (3. + r) / 4.);
-        acc = fmin(acc, 2.);
-        return fmax(0., acc);
-    }
-    }
-}
+// psi_eval (lib.rs:107-118): assembly.hpp, shared with the scalar arm's face correction
 
 struct MomentumArgs {
     const double *u, *v, *w, *gu, *flux, *pf, *a_di, *b_u_di, *b_v_di, *b_w_di;
@@ -1117,6 +1102,7 @@ int k_momentum(SolverState &s, double *peclet_host) {
     hipLaunchKernelGGL(reduce_minmax_k, dim3(1), dim3(64), 0, ctx().stream, s.partials.p, g, s.scal.p + 8);
     ORC_HIP(hipGetLastError());
     if (ref_pe) ORC_TRY(sum_reference(s.pe.p, s.n, s.scal.p + 8));
+    s.diagonals_assembled = true;
     if (s.transient && s.time_levels > 0) ORC_TRY(k_time_term(s));  // after the Peclet statistics, which exclude the time term
     if (peclet_host) {
         if (s.mesh->halo.active()) {  // statistics over the whole mesh: sum; max of (-min, max)
@@ -1192,14 +1178,14 @@ static int create_stream(hipStream_t *out, int role, int lane) {
 }
 
 static int solve_field_on(SolverState &s, DevBuf<double> &a, DevBuf<double> &b, DevBuf<double> &x, int eq, Arena &arena, SolveStats &stats,
-                          SolveSide *side, Arena *side_arena, const AmgHierarchy *prepared = nullptr) {
+                          SolveSide *side, Arena *side_arena, const AmgHierarchy *prepared = nullptr, const OrcSettings *settings = nullptr) {
     MatView A;
     A.P = s.mesh->pat.dev();
     A.val = a.p;
     A.symmetric = s.mesh->pat.symmetric;
     A.halo = s.mesh->halo.active() ? &s.mesh->halo : nullptr;
     A.persistent_pattern = true;
-    const OrcSettings &t = s.settings;
+    const OrcSettings &t = settings ? *settings : s.settings;  // the scalar arm solves with its own solver fields
     if (arena.empty()) ORC_TRY(arena.reset());  // nothing of the previous solve is alive: a fragmented reservation is folded into one chunk
     if (side_arena && side_arena->empty()) ORC_TRY(side_arena->reset());
     CtxDefaultsScope restore_defaults(ctx());  // this solver's guard, reduction order and GMRES restart for the solve only
@@ -1733,6 +1719,33 @@ int solver_iterate(SolverState &s, uint64_t iterations, double *report) {
         if (std::isnan(u_avg) || std::isnan(v_avg) || std::isnan(w_avg)) return ORC_ERR_SOLUTION_DIVERGED;  // :217-221
     }
     return ORC_OK;
+}
+
+// ------------------------------------------------------------------ scalar arm (scalar.hip)
+// The flux the momentum assembly would see for the current fields — grad p, then face_k<0> — written to the arm's own
+// buffers: the flow's gp, flux, pf, partials and scal keep their values.
+int k_scalar_face_flux(SolverState &s) {
+    OrcMesh &m = *s.mesh;
+    HaloPlan &H = m.halo;
+    const int64_t n = s.n;
+    SolverState::Scalar &c = s.sc;
+    if (H.active()) { double *f[4] = {s.u.p, s.v.p, s.w.p, s.p.p}; ORC_TRY(H.exchange(f, 4)); }
+    if (s.settings.gradient_reconstruction == ORC_GRAD_LEAST_SQUARES)
+        hipLaunchKernelGGL(grad_p_lsq_k, dim3(grid_for(s.n)), dim3(kBlock), 0, ctx().stream, m.dev(), s.p.p, c.gp.p, s.dev_status.p);
+    else
+        hipLaunchKernelGGL(grad_p_k, dim3(grid_for(s.n)), dim3(kBlock), 0, ctx().stream, m.dev(), s.p.p, c.gp.p, s.settings.q1_compat, s.dev_status.p);
+    ORC_HIP(hipGetLastError());
+    if (H.active()) { double *g3[3] = {c.gp.p, c.gp.p + n, c.gp.p + 2 * n}; ORC_TRY(H.exchange(g3, 3)); }
+    FaceArgs A{s.u.p, s.v.p, s.w.p, s.p.p, c.gp.p, s.du.p, s.dv.p, s.dw.p, s.settings.velocity_interpolation,
+               s.settings.pressure_interpolation, s.settings.q1_compat, s.rho};
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(face_k<0>), dim3(grid_for(m.n_faces)), dim3(kBlock), 0, ctx().stream, m.dev(), A, c.flux.p, c.pf.p,
+                       (double *)nullptr, s.dev_status.p);
+    ORC_HIP(hipGetLastError());
+    return ORC_OK;
+}
+
+int solve_scalar_system(SolverState &s, const OrcSettings &t) {
+    return solve_field_on(s, s.sc.a, s.sc.b, s.sc.phi, 4, s.arena, s.stats, &s.side, &s.side_arena, nullptr, &t);
 }
 
 // ------------------------------------------------------------------ solver::initialize_* (solver.rs:246-509, 710-772)

@@ -26,6 +26,26 @@ struct MeshDev {
     const double *zvec = nullptr;    // FaceZone.vector_value [3Z]
 };
 
+#ifdef __HIPCC__
+// the TVD limiters of settings::MomentumDiscretization (lib.rs:107-118): momentum_k and the scalar arm's scalar_face_k
+__device__ __forceinline__ double psi_eval(int momentum, double r) {
+    switch (momentum) {
+    case ORC_MOMENTUM_TVD_UD: return 0.;
+    case ORC_MOMENTUM_TVD_CD1: return 1.;
+    case ORC_MOMENTUM_TVD_LUD: return r;
+    case ORC_MOMENTUM_TVD_QUICK: return (3. + r) / 4.;
+    default: {  // UMIST; f64::min / max ignore NaN like fmin / fmax
+        double acc = INFINITY;
+        acc = fmin(acc, 2. * r);
+        acc = fmin(acc, (1. + 3. * r) / 4.);
+        acc = fmin(acc, (3. + r) / 4.);
+        acc = fmin(acc, 2.);
+        return fmax(0., acc);
+    }
+    }
+}
+#endif
+
 }  // namespace orc
 
 struct OrcMesh {
@@ -122,6 +142,30 @@ struct SolverState {
     int snap_time_levels = 0;
     double snap_time = 0.;
     bool snap_transient = false;
+    bool diagonals_assembled = false;  // k_momentum has written du/dv/dw at least once (Rhie-Chow face fluxes need them)
+    // Passive scalar transport (orc_solver_set_scalar, scalar.hip): off unless enabled; every buffer is the arm's own, so
+    // that nothing the flow reads is written.
+    struct Scalar {
+        bool on = false;
+        OrcScalarSettings c{};
+        DevBuf<double> phi, phi_old, lev[2], src;      // [n]
+        DevBuf<double> a, a_g;                          // SELL values: the system, its Gamma part (built once per configuration)
+        DevBuf<double> b, b_g;                          // [n]: the right-hand side, its Gamma part
+        DevBuf<double> grad;                            // [3][n] Green-Gauss grad phi (TVD)
+        DevBuf<double> gp, flux, pf, corr, bterm;       // the arm's grad p [3][n]; per face: flux, face pressure, c_f, boundary term
+        DevBuf<int32_t> zkind;                          // resolved OrcScalarBc per zone (VALUE, FLUX, ZERO_GRADIENT)
+        DevBuf<double> zval, partials, scal;
+        std::vector<int32_t> kind;                      // as set per zone (DEFAULT included)
+        std::vector<double> value;
+        std::vector<int32_t> resolved_kind;             // what a_g / b_g were built for
+        std::vector<double> resolved_value;
+        bool has_source = false;
+        int levels = 0;                                 // known previous levels, 0..2
+        double report[4] = {0., 0., 0., 0.};
+        DevBuf<double> snap_phi, snap_lev[2];
+        int snap_levels = 0;
+        bool snap_on = false;
+    } sc;
 };
 
 int mesh_upload(OrcMesh &m, int64_t n_own, int64_t n_cells, int64_t n_faces, int32_t n_zones, const int64_t *face_c0, const int64_t *face_c1,
@@ -146,6 +190,12 @@ int initialize_pressure_field_dev(SolverState &s);     // solver.rs:414-509
 int initialize_flow_dev(SolverState &s, uint64_t iteration_count);  // solver.rs:246-352
 int initialize_velocity_field_dev(SolverState &s);     // solver.rs:511-696 (psi in s.p_prime, velocities in s.u/v/w)
 int post_loop_gradients_dev(SolverState &s);           // solver.rs:227-242
+// scalar arm (scalar.hip): face_k<0>'s flux of the current fields into the arm's own gp / flux / pf (ghosts exchanged first)
+int k_scalar_face_flux(SolverState &s);
+// the linear solve of the scalar system (equation index 4: no sibling pairing, no p' hierarchy) with the settings `t`
+int solve_scalar_system(SolverState &s, const OrcSettings &t);
+// one scalar solve of orc_solver_advance (levels shifted first), the report kept in s.sc.report
+int scalar_step_dev(SolverState &s);
 
 }  // namespace orc
 

@@ -72,3 +72,27 @@ class Transient(C.Structure):
     @classmethod
     def make(cls, dt, scheme=TimeScheme.Euler, inner_iterations=20, inner_tolerance=0.0):
         return cls(dt=dt, scheme=scheme, reserved0=0, inner_iterations=inner_iterations, inner_tolerance=inner_tolerance)
+
+
+class ScalarBc:  # include/orc_types.h OrcScalarBc
+    DEFAULT, VALUE, FLUX, ZERO_GRADIENT = 0, 1, 2, 3
+
+
+class ScalarSettings(C.Structure):
+    """OrcScalarSettings: passive scalar transport on the solver's flow (Solver.set_scalar)."""
+    _fields_ = [
+        ("diffusivity", C.c_double), ("scheme", C.c_int32), ("solver_type", C.c_int32), ("preconditioner", C.c_int32),
+        ("reserved0", C.c_int32), ("iterations", C.c_uint64), ("relative_convergence_threshold", C.c_double),
+        ("relaxation", C.c_double), ("outer_iterations", C.c_uint64), ("outer_tolerance", C.c_double),
+    ]
+
+    @classmethod
+    def default(cls, **overrides):
+        """orc_scalar_settings_default (UD, BiCGSTAB + Jacobi, 500 iterations, 1e-10, outer 30 / 1e-8, Gamma 1e-3) with overrides"""
+        s = cls()
+        lib().orc_scalar_settings_default(C.byref(s))
+        for k, v in overrides.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s

@@ -125,6 +125,74 @@ class Solver:
             return rep if report else st
         return (st, rep) if report else st
 
+    # ---------------------------------------------------------------- passive scalar (orc_solver_set_scalar)
+    def set_scalar(self, settings=None, raise_on_error=True):
+        """a settings.ScalarSettings turns the scalar arm on (phi = 0, no source, no levels, every zone DEFAULT); None turns it off"""
+        st = lib().orc_solver_set_scalar(self.ptr, C.byref(settings) if settings is not None else None)
+        if raise_on_error:
+            check(st)
+        return st
+
+    def set_scalar_bc(self, zone, kind, value=0.0, raise_on_error=True):
+        """zone: index (orc_mesh_update_zones order) or name in the mesh's zone_names; kind: settings.ScalarBc"""
+        if isinstance(zone, str):
+            zone = list(self.mesh.arrays["zone_names"]).index(zone)
+        st = lib().orc_solver_set_scalar_bc(self.ptr, C.c_int32(zone), C.c_int32(kind), C.c_double(value))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def set_scalar_field(self, phi):
+        phi = _f64(phi)
+        check(lib().orc_solver_set_scalar_field(self.ptr, _p(phi)))
+
+    def get_scalar_field(self):
+        phi = np.empty(self.n)
+        check(lib().orc_solver_get_scalar_field(self.ptr, _p(phi)))
+        return phi
+
+    def set_scalar_source(self, source=None):
+        """source per unit volume in ORC cell order; None = no source"""
+        src = None if source is None else _f64(source)
+        check(lib().orc_solver_set_scalar_source(self.ptr, None if src is None else _p(src)))
+
+    def set_scalar_levels(self, phi_n, phi_nm1=None, raise_on_error=True):
+        """previous scalar levels (ORC cell order) of the step in progress; needs the transient and the scalar arm on"""
+        a, b = _f64(phi_n), None if phi_nm1 is None else _f64(phi_nm1)
+        st = lib().orc_solver_set_scalar_levels(self.ptr, _p(a), None if b is None else _p(b))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def solve_scalar(self, raise_on_error=True):
+        """one scalar solve -> [outer rounds used, last relative change, min phi, max phi] (with raise_on_error=False: (status, report))"""
+        rep = np.zeros(4)
+        st = lib().orc_solver_solve_scalar(self.ptr, _p(rep))
+        if raise_on_error:
+            check(st)
+            return rep
+        return st, rep
+
+    def last_scalar_report(self):
+        rep = np.zeros(4)
+        check(lib().orc_solver_last_scalar_report(self.ptr, _p(rep)))
+        return rep
+
+    def assemble_scalar(self, raise_on_error=True):
+        """(a in pattern order, b in the mesh's internal cell order) of the scalar system of the current state"""
+        a, b = np.empty(self.mesh.nnz), np.zeros(self.n)
+        st = lib().orc_solver_assemble_scalar(self.ptr, _p(a), _p(b))
+        if raise_on_error:
+            check(st)
+            return a, b
+        return st
+
+    def scalar_boundary_flux(self):
+        """per zone: the convective plus diffusive flux of phi into the domain"""
+        out = np.zeros(len(self.mesh.arrays["zone_type"]))
+        check(lib().orc_solver_scalar_boundary_flux(self.ptr, _p(out)))
+        return out
+
     def assemble_momentum(self):
         nnz, n = self.mesh.nnz, self.n
         au, av, aw = np.empty(nnz), np.empty(nnz), np.empty(nnz)
