@@ -421,6 +421,23 @@ int orc_debug_xwin_counters(long long out[3], int reset);
  * SIMPLE iteration share their pattern; when v's and w's fine pairings verify as u's, ONE symbolic pass carries the three value sets:
  * linear_algebra.rs:80-84 per system, bit-identical).  ORC_AMG_SHARED_GALERKIN=0 switches the shared pass off. */
 long long orc_debug_shared_galerkin(int reset);
+/* Test hook: product launches per kernel family since the last reset.  launch_spmv (orc_amd/csrc/linalg.hip) picks one of about a
+ * dozen instantiations by the matrix (raggedness class, narrow column image, mirrors) and by the call (scalings carried or materialised,
+ * non-temporal policy); the counters are incremented on the host where each launch is made, so a test that compares a product bit for
+ * bit can tell which kernel produced the bits.  out[f] for f < min(n_out, ORC_PRODUCT_FAMILIES) (further entries are zeroed); out may
+ * be null (reset only).  Returns ORC_PRODUCT_FAMILIES.  No device code; neither kernel arguments nor the dispatch depend on it. */
+enum {
+    ORC_PRODUCT_RAGGED = 0,         /* spmv_k<Epi, kSpmvRagged>: long ragged rows (class 1) without a mirror */
+    ORC_PRODUCT_PACKED = 1,         /* spmv_k<Epi, kSpmvPacked>: packed mirror without windows */
+    ORC_PRODUCT_WINDOW = 2,         /* spmv_xwin_k: packed mirror with LDS x windows */
+    ORC_PRODUCT_GENERIC_SCALED = 3, /* spmv_uniform_k<Epi, false>: scalings applied on the fly (32-bit columns) */
+    ORC_PRODUCT_WIDE = 4,           /* spmv_uniform_k<Epi, false, false, false, false>: unscaled, 32-bit columns */
+    ORC_PRODUCT_NARROW = 5,         /* spmv_uniform_k<Epi, false, false, true, false>: unscaled, narrow column image */
+    ORC_PRODUCT_NARROW_NT = 6,      /* the same with non-temporal matrix loads */
+    ORC_PRODUCT_MESH = 7,           /* every persistent-pattern (level-0 mesh) variant */
+    ORC_PRODUCT_FAMILIES = 8
+};
+int orc_debug_product_launches(long long *out, int n_out, int reset);
 /* kernel-level timers accumulated inside orc_solver_iterate when enabled: name/ms pairs */
 int orc_profile_enable(int on);
 int orc_profile_report(char *buf, int64_t buf_len);

@@ -396,6 +396,20 @@ struct EpiTs {  // t = A s ; partials t.s, t.t            (linear_algebra.rs:260
     }
 };
 
+// Host-side launch counters of launch_spmv, one per kernel family (orc_debug_product_launches, include/orc_amd.h: ORC_PRODUCT_*): a test
+// that compares a product bit for bit has to know WHICH kernel produced the bits.  Counted where the launch is made; no device code.
+enum { kFamRagged = 0, kFamPacked, kFamWindow, kFamGenericScaled, kFamWide, kFamNarrow, kFamNarrowNT, kFamMesh, kFamCount };
+static std::atomic<long long> g_product_launches[kFamCount];
+static inline void count_launch(int family) { g_product_launches[family].fetch_add(1, std::memory_order_relaxed); }
+int debug_product_launches(long long *out, int n_out, bool reset) {
+    for (int f = 0; f < kFamCount; ++f) {
+        const long long v = reset ? g_product_launches[f].exchange(0, std::memory_order_relaxed) : g_product_launches[f].load(std::memory_order_relaxed);
+        if (out && f < n_out) out[f] = v;
+    }
+    for (int f = kFamCount; out && f < n_out; ++f) out[f] = 0;
+    return kFamCount;
+}
+
 template <class Epi>
 static int launch_spmv(const MatView &A_in, const double *x, const Epi &epi, double *partials, int *grid_out, const double *skip_flags = nullptr) {
     MatView A = A_in;
@@ -468,6 +482,7 @@ static int launch_spmv(const MatView &A_in, const double *x, const Epi &epi, dou
         const bool exchange_first = !comm_host_transport_active();
         if (exchange_first) ORC_TRY(H->exchange(const_cast<double *>(x)));  // C1 on the library stream (every RCCL call stays there)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false>), dim3(g_i), dim3(kBlock), 0, aux, V, x, epi, partials, skip_flags);
+        count_launch(kFamGenericScaled);
         ORC_HIP(hipEventRecord((hipEvent_t)H->ev_done, aux));
         if (!exchange_first) {
             const int ex = H->exchange(const_cast<double *>(x));
@@ -478,8 +493,10 @@ static int launch_spmv(const MatView &A_in, const double *x, const Epi &epi, dou
         }
         V.slice_lo = 0; V.slice_hi = H->interior_lo; V.part_base = g_i;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false>), dim3(g_b), dim3(kBlock), 0, lib, V, x, epi, partials, skip_flags);
+        count_launch(kFamGenericScaled);
         V.slice_lo = H->interior_hi; V.slice_hi = A.P.n_slices; V.part_base = g_i + g_b;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false>), dim3(g_b), dim3(kBlock), 0, lib, V, x, epi, partials, skip_flags);
+        count_launch(kFamGenericScaled);
         ORC_HIP(hipStreamWaitEvent(lib, (hipEvent_t)H->ev_done, 0));
         ORC_HIP(hipGetLastError());
         ctx().halo_overlaps += 1;
@@ -493,14 +510,17 @@ static int launch_spmv(const MatView &A_in, const double *x, const Epi &epi, dou
         if (!A.s1 && !A.s2 && A.nt) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_xwin_k<Epi, false, true>), dim3(g), dim3(kBlock), xwin_smem, ctx().stream, A, x, epi, partials, skip_flags);
         else if (!A.s1 && !A.s2) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_xwin_k<Epi, false>), dim3(g), dim3(kBlock), xwin_smem, ctx().stream, A, x, epi, partials, skip_flags);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_xwin_k<Epi>), dim3(g), dim3(kBlock), xwin_smem, ctx().stream, A, x, epi, partials, skip_flags);
+        count_launch(kFamWindow);
         ORC_HIP(hipGetLastError());
         return ORC_OK;
     }
-    if (A.pk.ptr)
+    if (A.pk.ptr) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_k<Epi, kSpmvPacked>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
-    else if (A.P.ragged == 1)  // long ragged rows without a mirror: every slot clamped, nothing skipped
+        count_launch(kFamPacked);
+    } else if (A.P.ragged == 1) {  // long ragged rows without a mirror: every slot clamped, nothing skipped
         hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_k<Epi, kSpmvRagged>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
-    else if (A.persistent_pattern) {  // mesh-pattern matrices (level 0): wave-uniform loads, predicated gathers
+        count_launch(kFamRagged);
+    } else if (A.persistent_pattern) {  // mesh-pattern matrices (level 0): wave-uniform loads, predicated gathers
         const bool narrow = A.P.col16 != nullptr, scaled = A.s1 || A.s2;
         if (narrow && !scaled && A.nt) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false, true, true, false, true>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
         else if (narrow && !scaled) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false, true, true, false>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
@@ -508,14 +528,18 @@ static int launch_spmv(const MatView &A_in, const double *x, const Epi &epi, dou
         else if (!scaled && A.nt) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false, true, false, false, true>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
         else if (!scaled) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false, true, false, false>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false, true>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
-    }
-    else if (!(A.s1 || A.s2) && A.P.col16) {  // first coarse level, scaled values materialised, narrow column image
+        count_launch(kFamMesh);
+    } else if (!(A.s1 || A.s2) && A.P.col16) {  // first coarse level, scaled values materialised, narrow column image
         if (A.nt) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false, false, true, false, true>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false, false, true, false>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
-    } else if (!(A.s1 || A.s2))  // short ragged rows (first coarse level): the same kernel under its own name; scaled values materialised
+        count_launch(A.nt ? kFamNarrowNT : kFamNarrow);
+    } else if (!(A.s1 || A.s2)) {  // short ragged rows (first coarse level): the same kernel under its own name; scaled values materialised
         hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false, false, false, false>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
-    else
+        count_launch(kFamWide);
+    } else {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_uniform_k<Epi, false>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);
+        count_launch(kFamGenericScaled);
+    }
     ORC_HIP(hipGetLastError());
     return ORC_OK;
 }

@@ -10,6 +10,7 @@ namespace orc {
 void debug_amg_certification(long long out[2], bool reset);  // amg.hip
 long long debug_shared_galerkin(bool reset);                   // amg.hip
 int debug_xwin_counters(long long out[3], bool reset);       // amg.hip
+int debug_product_launches(long long *out, int n_out, bool reset);  // linalg.hip
 
 static thread_local Ctx *t_ctx_override = nullptr;
 
@@ -360,6 +361,11 @@ int orc_debug_xwin_counters(long long out[3], int reset) {
     if (!out) return orc::set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
     ORC_TRY(orc::ensure_init());
     return orc::debug_xwin_counters(out, reset != 0);
+}
+
+int orc_debug_product_launches(long long *out, int n_out, int reset) {
+    if (n_out < 0 || (!out && n_out > 0)) { orc::set_error(ORC_ERR_BAD_ARGUMENT, "null argument"); return -1; }
+    return orc::debug_product_launches(out, n_out, reset != 0);
 }
 
 // Which of the library's streams still hold work (hipStreamQuery: never blocks), one line each: "<name> priority <p> busy|idle".  Meant for a

@@ -191,3 +191,15 @@ def amg_certification(reset=False):
     out = (C.c_longlong * 2)()
     check(lib().orc_debug_amg_certification(out, C.c_int(1 if reset else 0)))
     return out[0], out[1]
+
+
+PRODUCT_FAMILIES = ("ragged", "packed", "window", "generic_scaled", "wide", "narrow", "narrow_nt", "mesh")  # include/orc_amd.h ORC_PRODUCT_*
+
+
+def product_launches(reset=False):
+    """Test hook: {family: product launches since the last reset} (orc_debug_product_launches; the families are launch_spmv's kernels)"""
+    out = (C.c_longlong * len(PRODUCT_FAMILIES))()
+    n = lib().orc_debug_product_launches(out, C.c_int(len(PRODUCT_FAMILIES)), C.c_int(1 if reset else 0))
+    if n != len(PRODUCT_FAMILIES):
+        raise RuntimeError("orc_debug_product_launches: %d families, %d expected" % (n, len(PRODUCT_FAMILIES)))
+    return dict(zip(PRODUCT_FAMILIES, (int(v) for v in out)))
