@@ -218,6 +218,28 @@ int64_t orc_last_jacobi_sweeps(void);
 int orc_set_gmres_restart(int m);
 /* the last orc_iterative_solve's GMRES arm: Arnoldi steps, cycles, beta0 and the final residual estimate |g| */
 int orc_last_gmres_stats(int64_t *steps, int64_t *cycles, double *initial_residual, double *final_estimate);
+/* ORC_SOLVER_CG (extension, no reference counterpart): preconditioned conjugate gradients for a symmetric positive definite
+ * system — what build_pressure_correction_matrices (discretization.rs:359-448) and a pure-conduction scalar system are.
+ *  - CG does NOT test the symmetry of the values: on a non-symmetric or indefinite matrix it runs until p.q <= 0 (event 1)
+ *    or until the iterations are spent, and what it returns is then no Krylov minimiser of anything.
+ *  - preconditioner: the other arms apply ORC_PRECOND_JACOBI as the left scaling p_inv * a, which destroys symmetry.  This
+ *    arm keeps the operator unscaled and applies M = D inside the recurrence: z = D^-1 r (JACOBI) or z = r (NONE).  A view
+ *    that arrives already scaled (CG nested inside another arm) is ORC_ERR_BAD_ARGUMENT; a diagonal entry that is missing,
+ *    zero or non-finite under JACOBI is ORC_ERR_STRUCTURAL_ZERO.  relaxation_factor and reduction_order play no part: the
+ *    sums are per-workgroup trees folded in a fixed order, as for GMRES.
+ *  - start: r = b - A x, z = M^-1 r, p = z, rho = r.z, beta0 = |r|.  Iteration k: q = A p; alpha = rho / p.q; x += alpha p;
+ *    r -= alpha q; z = M^-1 r; rho' = r.z; p = z + (rho' / rho) p.
+ *  - stops, all decided on the device: beta0 == 0 (no iteration, x untouched); after the update of an iteration, which
+ *    counts, |r| <= convergence_threshold * beta0 (never with a threshold <= 0); iteration_count reached; and the events.
+ *    Event 1: p.q <= 0.  Event 2: rho or p.q is non-finite, or alpha overflows.  Both are tested before the update, so x keeps the last
+ *    completed iterate and that iteration does not count.  Event 2 is also raised right after an update whose r.z or r.r
+ *    came out non-finite (that iteration counts).  An event is recorded in orc_last_cg_stats and the status stays ORC_OK.
+ *  - iteration_count == 0 or n == 0 leaves x unchanged.  At most three launches per iteration (product with the p.q partial
+ *    sums, cg_update_k, cg_direction_k), no float atomics (two solves of one system give identical bits), one host
+ *    synchronisation at the end of the solve.
+ * orc_last_cg_stats: completed iterations, beta0, the final recurrence residual |r| and the event of the last CG solve of
+ * this process (orc_iterative_solve, or a solver's system solved with ORC_SOLVER_CG).  Any pointer may be NULL. */
+int orc_last_cg_stats(int64_t *iterations, double *initial_residual, double *final_residual, int32_t *event);
 /* y = A x: the `&CsrMatrix * &DVector` product the reference takes from nalgebra-sparse
  * (linear_algebra.rs:256,260); row sums accumulate in ascending-column order from 0.0, so y is
  * bit-identical to the CPU product.  `reps` > 1 repeats the launch (timing); avg_ms may be NULL. */
@@ -301,6 +323,24 @@ int orc_solver_iterate(OrcSolver *s, uint64_t iterations, double *report);
  * bench.py times the same iteration repeatedly, so that every step does identical work. */
 int orc_solver_snapshot(OrcSolver *s);
 int orc_solver_restore(OrcSolver *s);
+/* A linear solver of its own for the pressure correction (new-build extension, orc_types.h OrcLinearSolver).  The p' matrix is
+ * symmetric positive definite (discretization.rs:401-438: a_PN is symmetric in P and N), the momentum matrices are not, and
+ * the reference solves all four with one MatrixSolverSettings (solver.rs:99-179).
+ *  - orc_solver_set_pressure_solver(s, c): c == NULL removes the override.  Otherwise c is validated (a solver type of
+ *    OrcSolutionMethod that iterative_solve knows, a known preconditioner, iterations >= 1, threshold >= 0 and not NaN, a
+ *    finite relaxation: ORC_ERR_BAD_ARGUMENT otherwise, solver unchanged) and from then on every p' solve
+ *    (orc_solver_iterate, orc_solver_advance) runs with these five fields in
+ *    place of the settings'.  The momentum solves and their schedule keep following OrcSettings.solver_type.
+ *  - the p' Multigrid hierarchy is set up ahead of the solve only when the method that will solve p' is a Multigrid arm.
+ *  - a solver that never sets the override launches exactly what it launched before; an override equal to the settings'
+ *    own fields changes no bit.  On a partitioned mesh every rank must set the same override.
+ *  - orc_solver_snapshot / orc_solver_restore do not touch it.
+ * orc_solver_get_pressure_solver: *enabled = 1 and the override, or 0 and the five fields of the settings.
+ * orc_solver_debug_pressure_hierarchies (test hook): p' Multigrid hierarchies this solver has set up so far, ahead of a solve or
+ * inside one. */
+int orc_solver_set_pressure_solver(OrcSolver *s, const OrcLinearSolver *c);
+int orc_solver_get_pressure_solver(OrcSolver *s, OrcLinearSolver *c, int32_t *enabled);
+long long orc_solver_debug_pressure_hierarchies(OrcSolver *s);
 /* individual phases, for the parity tests: matrices come back in pattern order */
 int orc_solver_assemble_momentum(OrcSolver *s, double *a_u, double *a_v, double *a_w, double *b_u, double *b_v, double *b_w, double peclet[3]);
 int orc_solver_assemble_pressure(OrcSolver *s, double *a_p, double *b_p);

@@ -65,7 +65,8 @@ enum OrcSolutionMethod {
     ORC_SOLVER_MULTICOLOR_GS = 16,         /* multicolour Gauss-Seidel sweeps */
     ORC_SOLVER_BICGSTAB_GS_PRECOND = 17,   /* right-preconditioned BiCGSTAB, M = one multicolour GS sweep */
     ORC_SOLVER_MULTIGRID_GS = 18,          /* Multigrid arm with multicolour GS as the smoother */
-    ORC_SOLVER_GMRES = 19                  /* restarted GMRES(m), CGS2 Arnoldi, relative stopping test (orc_amd.h: orc_set_gmres_restart) */
+    ORC_SOLVER_GMRES = 19,                 /* restarted GMRES(m), CGS2 Arnoldi, relative stopping test (orc_amd.h: orc_set_gmres_restart) */
+    ORC_SOLVER_CG = 20                     /* preconditioned conjugate gradients for symmetric positive definite systems (orc_amd.h: orc_last_cg_stats) */
 };
 
 /* settings::PreconditionMethod (lib.rs:181-185) */
@@ -191,6 +192,17 @@ typedef struct OrcScalarSettings {
     uint64_t outer_iterations;             /* >= 1: Picard rounds of a TVD solve at most; default 30 */
     double outer_tolerance;                /* >= 0: stop once |phi_new - phi_old|_2 <= outer_tolerance |phi_new|_2; default 1e-8 */
 } OrcScalarSettings;
+
+/* A linear solver of its own for ONE system of the SIMPLE iteration (new-build extension; the reference's solve_steady has one
+ * MatrixSolverSettings for all four systems, solver.rs:99-179).  orc_amd.h: orc_solver_set_pressure_solver — the pressure
+ * correction is symmetric positive definite, the momentum systems are not, so ORC_SOLVER_CG can serve the one and not the others. */
+typedef struct OrcLinearSolver {
+    int32_t solver_type;    /* OrcSolutionMethod */
+    int32_t preconditioner; /* OrcPreconditionMethod */
+    uint64_t iterations;    /* >= 1 */
+    double relative_convergence_threshold; /* >= 0 */
+    double relaxation;
+} OrcLinearSolver;
 
 #ifdef __cplusplus
 }

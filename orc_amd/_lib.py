@@ -43,6 +43,17 @@ def lib():
         for name in ("orc_mesh_n_cells", "orc_mesh_nnz", "orc_last_jacobi_sweeps"):
             if hasattr(L, name):
                 getattr(L, name).restype = C.c_int64
+        # entries added with the CG arm and the p' solver override: full signatures
+        if hasattr(L, "orc_last_cg_stats"):
+            L.orc_last_cg_stats.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+            L.orc_last_cg_stats.restype = C.c_int
+        if hasattr(L, "orc_solver_set_pressure_solver"):
+            L.orc_solver_set_pressure_solver.argtypes = [C.c_void_p, C.c_void_p]
+            L.orc_solver_set_pressure_solver.restype = C.c_int
+            L.orc_solver_get_pressure_solver.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+            L.orc_solver_get_pressure_solver.restype = C.c_int
+            L.orc_solver_debug_pressure_hierarchies.argtypes = [C.c_void_p]
+            L.orc_solver_debug_pressure_hierarchies.restype = C.c_longlong
         _lib = L
     return _lib
 

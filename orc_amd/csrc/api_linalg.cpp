@@ -262,4 +262,13 @@ int orc_last_gmres_stats(int64_t *steps, int64_t *cycles, double *initial_residu
     return ORC_OK;
 }
 
+int orc_last_cg_stats(int64_t *iterations, double *initial_residual, double *final_residual, int32_t *event) {
+    const orc::SolveStats &s = orc::g_last_stats;
+    if (iterations) *iterations = s.cg_iterations;
+    if (initial_residual) *initial_residual = s.cg_beta0;
+    if (final_residual) *final_residual = s.cg_residual;
+    if (event) *event = s.cg_event;
+    return ORC_OK;
+}
+
 }  // extern "C"

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <memory>
 
 #include "assembly.hpp"
@@ -332,6 +333,48 @@ int orc_solver_assemble_pressure(OrcSolver *s, double *a_p, double *b_p) {
     if (b_p) ORC_TRY(t.b_p.download(b_p, (size_t)t.n));
     return fetch_status(t);
 }
+
+// ---------------------------------------------------------------- a linear solver of its own for p' (OrcLinearSolver)
+static_assert(sizeof(OrcLinearSolver) == 32 && offsetof(OrcLinearSolver, solver_type) == 0 && offsetof(OrcLinearSolver, preconditioner) == 4 &&
+                  offsetof(OrcLinearSolver, iterations) == 8 && offsetof(OrcLinearSolver, relative_convergence_threshold) == 16 &&
+                  offsetof(OrcLinearSolver, relaxation) == 24,
+              "OrcLinearSolver is part of the ABI (orc_amd/settings.py LinearSolver mirrors it)");
+int orc_solver_set_pressure_solver(OrcSolver *s, const OrcLinearSolver *c) {
+    if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
+    SolverState &st = s->st;
+    if (!c) {  // back to the settings' own solver: the loop launches what it launched before
+        st.p_solver_on = false;
+        st.p_solver = OrcLinearSolver{};
+        return ORC_OK;
+    }
+    const int m = c->solver_type;
+    if (!(m == ORC_SOLVER_GAUSS_SEIDEL || m == ORC_SOLVER_JACOBI || m == ORC_SOLVER_MULTIGRID || m == ORC_SOLVER_BICGSTAB ||
+          m == ORC_SOLVER_MULTICOLOR_GS || m == ORC_SOLVER_BICGSTAB_GS_PRECOND || m == ORC_SOLVER_MULTIGRID_GS || m == ORC_SOLVER_GMRES ||
+          m == ORC_SOLVER_CG))
+        return set_error(ORC_ERR_BAD_ARGUMENT, "pressure solver: unknown solver type %d", m);
+    if (c->preconditioner != ORC_PRECOND_NONE && c->preconditioner != ORC_PRECOND_JACOBI)
+        return set_error(ORC_ERR_BAD_ARGUMENT, "pressure solver: unknown preconditioner %d", c->preconditioner);
+    if (c->iterations == 0) return set_error(ORC_ERR_BAD_ARGUMENT, "pressure solver: iterations must be at least 1");
+    if (!(c->relative_convergence_threshold >= 0.)) return set_error(ORC_ERR_BAD_ARGUMENT, "pressure solver: relative_convergence_threshold must be >= 0");
+    if (!std::isfinite(c->relaxation)) return set_error(ORC_ERR_BAD_ARGUMENT, "pressure solver: relaxation must be finite");
+    st.p_solver = *c;
+    st.p_solver_on = true;
+    return ORC_OK;
+}
+
+int orc_solver_get_pressure_solver(OrcSolver *s, OrcLinearSolver *c, int32_t *enabled) {
+    if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
+    const SolverState &st = s->st;
+    if (enabled) *enabled = st.p_solver_on ? 1 : 0;
+    if (c) {
+        const OrcSettings t = st.p_settings();
+        c->solver_type = t.solver_type; c->preconditioner = t.preconditioner; c->iterations = t.iterations;
+        c->relative_convergence_threshold = t.relative_convergence_threshold; c->relaxation = t.relaxation;
+    }
+    return ORC_OK;
+}
+
+long long orc_solver_debug_pressure_hierarchies(OrcSolver *s) { return s ? s->st.p_hierarchy_setups : 0; }
 
 // ---------------------------------------------------------------- implicit time stepping (OrcTransient)
 int orc_solver_set_transient(OrcSolver *s, const OrcTransient *t) {

@@ -1254,8 +1254,9 @@ static int prepare_p_hierarchy(SolverState &s) {
     Arena &scratch = s.p_scratch_shared ? s.lanes[0].scratch_arena : s.hier_scratch;
     scratch.release(Arena::Mark{0, 0});
     ORC_TRY(scratch.reset());
-    ORC_TRY(multigrid_prepare_dev(A, s.settings.preconditioner, s.hier_arena, s.p_hierarchy, nullptr, 0, &scratch));
+    ORC_TRY(multigrid_prepare_dev(A, s.p_settings().preconditioner, s.hier_arena, s.p_hierarchy, nullptr, 0, &scratch));
     ORC_HIP(hipStreamSynchronize(st));
+    s.p_hierarchy_setups += 1;
     return ORC_OK;
 }
 
@@ -1637,10 +1638,13 @@ int solver_iterate(SolverState &s, uint64_t iterations, double *report) {
         ORC_TRY(k_momentum(s, report ? peclet : nullptr));       // :61-82
         if (H.active()) { double *d3[3] = {s.du.p, s.dv.p, s.dw.p}; ORC_TRY(H.exchange(d3, 3)); }
         if (dbg) { debug_field(s, "b_u", s.b_u); debug_field(s, "b_v", s.b_v); debug_field(s, "b_w", s.b_w); }
-        const int method = s.settings.solver_type;
+        const int method = s.settings.solver_type;  // the momentum systems' (and their schedule's)
+        const OrcSettings p_set = s.p_settings();   // the pressure correction's: the settings, or orc_solver_set_pressure_solver's override
+        const int method_p = p_set.solver_type;
+        const bool p_multigrid = method_p == ORC_SOLVER_MULTIGRID || method_p == ORC_SOLVER_MULTIGRID_GS;
         PrepareThread prep;
         s.p_hierarchy.n_levels = 0;
-        const bool early_p = s.early_p_hierarchy && (method == ORC_SOLVER_MULTIGRID || method == ORC_SOLVER_MULTIGRID_GS) && !dbg && !ctx().profile;
+        const bool early_p = s.early_p_hierarchy && p_multigrid && !dbg && !ctx().profile;
         if (early_p && !s.prep_stream) ORC_TRY(create_stream(&s.prep_stream, kSetupStream, 2));
         const bool lanes_ok = s.concurrent_momentum && !H.active() && !dbg && !ctx().profile &&
                               (method == ORC_SOLVER_MULTIGRID || method == ORC_SOLVER_BICGSTAB || method == ORC_SOLVER_JACOBI ||
@@ -1659,7 +1663,7 @@ int solver_iterate(SolverState &s, uint64_t iterations, double *report) {
         // The p' hierarchy is needed after the momentum solves.  Beside the per-system lanes it is built from the start; in the
         // lock-step schedule the momentum set-ups are the critical path of the first phase (nothing bandwidth-bound but the
         // level-0 solve runs beside them), so it starts when they are through and runs beside the bandwidth-bound coarse levels.
-        const bool p_late = early_p && triple_ok && method == ORC_SOLVER_MULTIGRID;
+        const bool p_late = early_p && triple_ok && method == ORC_SOLVER_MULTIGRID && method_p == ORC_SOLVER_MULTIGRID;
         s.p_scratch_shared = p_late;
         if (early_p && !p_late) {
             ORC_HIP(hipStreamSynchronize(ctx().stream));  // the diagonals (and their ghosts) are in place
@@ -1697,7 +1701,9 @@ int solver_iterate(SolverState &s, uint64_t iterations, double *report) {
         ORC_TRY(vec_fill(s.p_prime.p, 0., s.n));                 // :167
         if (dbg) debug_field(s, "b_p", s.b_p);
         ORC_TRACE("p' solve");
-        ORC_TRY(solve_field(s, s.a_p, s.b_p, s.p_prime, 3));        // :168-179
+        if (p_multigrid && s.p_hierarchy.n_levels == 0) s.p_hierarchy_setups += 1;  // no prepared hierarchy: the arm sets one up inside the solve
+        ORC_TRY(solve_field_on(s, s.a_p, s.b_p, s.p_prime, 3, s.arena, s.stats, &s.side, &s.side_arena, nullptr,
+                               s.p_solver_on ? &p_set : nullptr));  // :168-179
         ORC_TRACE("p' solve done");
         if (dbg) debug_field(s, "p_prime", s.p_prime);
         if (H.active()) ORC_TRY(H.exchange(s.p_prime.p));

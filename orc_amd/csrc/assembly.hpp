@@ -123,6 +123,22 @@ struct SolverState {
     SolveSide side;       // the same for the solves on the library stream (p', or all four when the lanes are off)
     Arena side_arena;
     bool two_stream_multigrid = true;
+    // A linear solver of its own for the pressure correction (orc_solver_set_pressure_solver): off unless set.  The momentum schedule
+    // keeps following settings.solver_type; the p' solve and the decision about its early hierarchy follow p_settings().
+    bool p_solver_on = false;
+    OrcLinearSolver p_solver{};
+    OrcSettings p_settings() const {  // the settings the p' solve runs with
+        OrcSettings t = settings;
+        if (p_solver_on) {
+            t.solver_type = p_solver.solver_type; t.preconditioner = p_solver.preconditioner; t.iterations = p_solver.iterations;
+            t.relative_convergence_threshold = p_solver.relative_convergence_threshold; t.relaxation = p_solver.relaxation;
+        }
+        return t;
+    }
+    // Test hook (orc_solver_debug_pressure_hierarchies): p' hierarchies set up so far.  A set-up ahead of the solve is counted where it
+    // ran (prepare of the p' hierarchy); one inside the solve is INFERRED, not observed: the iteration loop counts a p' solve by a
+    // Multigrid arm that finds no prepared hierarchy, because that arm then builds its own.
+    long long p_hierarchy_setups = 0;
     bool concurrent_momentum = true;
     ~SolverState();
     uint64_t iterations_done = 0;

@@ -195,6 +195,18 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
 }
+// owned-row pair (e, e + 1), e even, of a 16-byte aligned vector: one 16-byte access, a scalar one for the last element of an odd
+// length; zeros past n (ghost entries and padding take no part in any sum).  The vector kernels of gmres.hip and cg.hip.
+__device__ __forceinline__ double2 load2(const double *__restrict__ p, int64_t e, int64_t n) {
+    if (e + 1 < n) return *reinterpret_cast<const double2 *>(p + e);
+    double2 r = make_double2(0., 0.);
+    if (e < n) r.x = p[e];
+    return r;
+}
+__device__ __forceinline__ void store2(double *__restrict__ p, int64_t e, int64_t n, double2 v) {
+    if (e + 1 < n) *reinterpret_cast<double2 *>(p + e) = v;
+    else if (e < n) p[e] = v.x;
+}
 // max that keeps a NaN (fmax drops it): the reference's max_by(total_cmp) ranks NaN above every number
 __device__ __forceinline__ double max_nan(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : fmax(a, b); }
 __device__ __forceinline__ double wave_max(double v) {

@@ -47,18 +47,6 @@ enum {
 
 static __device__ __forceinline__ bool gmres_skip(const double *f) { return f[0] != 0. || f[1] != 0.; }
 
-// owned-row pair (e, e + 1), e even: zeros past n (ghost entries and padding take no part in any sum)
-static __device__ __forceinline__ double2 load2(const double *__restrict__ p, int64_t e, int64_t n) {
-    if (e + 1 < n) return *reinterpret_cast<const double2 *>(p + e);
-    double2 r = make_double2(0., 0.);
-    if (e < n) r.x = p[e];
-    return r;
-}
-static __device__ __forceinline__ void store2(double *__restrict__ p, int64_t e, int64_t n, double2 v) {
-    if (e + 1 < n) *reinterpret_cast<double2 *>(p + e) = v;
-    else if (e < n) p[e] = v.x;
-}
-
 // wave k of the workgroup owns the basis vectors q = k, k + 4, ...; its lane sums feed partials[q * gridDim.x + blockIdx.x]
 static __device__ __forceinline__ void gmres_write_dots(const double (&acc)[kGmresQPerWave], int nq, double *__restrict__ partials) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -395,6 +395,15 @@ struct EpiTs {  // t = A s ; partials t.s, t.t            (linear_algebra.rs:260
         r1 += acc * acc;
     }
 };
+struct EpiStoreDot {  // y = A x ; partial sum(y * s)             (q = A p, p . q : the CG arm, cg.hip)
+    static constexpr int kReductions = 1;
+    const double *s;
+    double *y;
+    __device__ __forceinline__ void apply(int64_t row, double acc, double &r0, double &) const {
+        y[row] = acc;
+        r0 += acc * s[row];
+    }
+};
 
 // Host-side launch counters of launch_spmv, one per kernel family (orc_debug_product_launches, include/orc_amd.h: ORC_PRODUCT_*): a test
 // that compares a product bit for bit has to know WHICH kernel produced the bits.  Counted where the launch is made; no device code.
@@ -555,6 +564,10 @@ int gmres_product_dev(const MatView &A, const double *x, double *y, const double
 }
 int gmres_residual_dev(const MatView &A, const double *b, const double *x, double *r, double *partials, int *grid, const double *skip_flags) {
     return launch_spmv(A, x, EpiResidualNorm{b, r}, partials, grid, skip_flags);
+}
+// the CG arm's product (cg.hip): q = A p with the partial sums of p . q, a no-op under skip_flags
+int cg_product_dev(const MatView &A, const double *p, double *q, double *partials, int *grid, const double *skip_flags) {
+    return launch_spmv(A, p, EpiStoreDot{p, q}, partials, grid, skip_flags);
 }
 
 int residual_dev(const MatView &A, const double *b, const double *x, double *r) {
@@ -1711,11 +1724,16 @@ int gs_arm_dev(const MatView &A, const double *b, double *x, uint64_t iteration_
                Arena &arena);  // gs.hip (extension)
 int gmres_dev(const MatView &A, const double *b, double *x, uint64_t iteration_count, double convergence_threshold, Arena &arena,
               SolveStats *stats);  // gmres.hip (extension)
+int cg_dev(const MatView &A, const double *b, double *x, uint64_t iteration_count, double convergence_threshold, int preconditioner, Arena &arena,
+           SolveStats *stats);  // cg.hip (extension)
 
 static int iterative_solve_body(const MatView &A_in, const double *b_in, double *x, uint64_t iteration_count, int method,
                                 double relaxation_factor, double convergence_threshold, int preconditioner, Arena &arena,
                                 SolveStats *stats) {
     const int64_t n = A_in.P.n;
+    // extension: CG keeps the operator symmetric — no left scaling, M = D inside the recurrence; relaxation_factor and reduction_order
+    // play no part (tree sums always)
+    if (method == ORC_SOLVER_CG) return cg_dev(A_in, b_in, x, iteration_count, convergence_threshold, preconditioner, arena, stats);
     ArenaScope scope(arena);
     MatView A = A_in;
     const double *b = b_in;

@@ -248,6 +248,9 @@ struct SolveStats {
     int64_t jacobi_sweeps = 0;
     int64_t gmres_steps = 0, gmres_cycles = 0;  // GMRES arm: Arnoldi steps and cycles run, beta_0 and the final |g| estimate
     double gmres_beta0 = 0., gmres_estimate = 0.;
+    int64_t cg_iterations = 0;  // CG arm: completed iterations, beta_0, the final recurrence |r| and the event (0 none, 1 p.q <= 0, 2 non-finite)
+    double cg_beta0 = 0., cg_residual = 0.;
+    int cg_event = 0;
     int amg_levels = 0;
     int64_t amg_rows[8] = {0};
     int64_t amg_nnz[8] = {0};

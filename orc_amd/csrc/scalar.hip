@@ -10,6 +10,8 @@
 //                       rounding) and the per-face boundary term of the boundary-flux report
 //   scalar_k            one thread per row: Gamma part + UD / CD1 convection + both sides' c_f + source + time term
 // DESIGN.md "Passive scalar transport" has the discretisation and the bytes of every pass.
+// The system is symmetric only without convection (a flow at rest: the Gamma part alone, plus the time term on the diagonal):
+// OrcScalarSettings.solver_type = ORC_SOLVER_CG is accepted for every configuration, and CG does not test symmetry (cg.hip).
 #include <algorithm>
 #include <cmath>
 
@@ -414,7 +416,7 @@ int validate(const OrcScalarSettings &c) {
         return set_error(ORC_ERR_UNSUPPORTED_SCHEME, "scalar: unsupported scheme %d", c.scheme);
     const int m = c.solver_type;
     if (!(m == ORC_SOLVER_JACOBI || m == ORC_SOLVER_MULTIGRID || m == ORC_SOLVER_BICGSTAB || m == ORC_SOLVER_MULTICOLOR_GS ||
-          m == ORC_SOLVER_BICGSTAB_GS_PRECOND || m == ORC_SOLVER_MULTIGRID_GS || m == ORC_SOLVER_GMRES))
+          m == ORC_SOLVER_BICGSTAB_GS_PRECOND || m == ORC_SOLVER_MULTIGRID_GS || m == ORC_SOLVER_GMRES || m == ORC_SOLVER_CG))
         return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: unknown solver type %d", m);
     if (c.preconditioner != ORC_PRECOND_NONE && c.preconditioner != ORC_PRECOND_JACOBI)
         return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: unknown preconditioner %d", c.preconditioner);

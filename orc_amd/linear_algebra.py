@@ -93,6 +93,14 @@ def last_gmres_stats():
     return steps.value, cycles.value, beta0.value, est.value
 
 
+def last_cg_stats():
+    """(completed iterations, beta0, final recurrence residual |r|, event: 0 none, 1 p.q <= 0, 2 non-finite) of the last CG solve"""
+    its, ev = C.c_int64(0), C.c_int32(0)
+    beta0, res = C.c_double(0.0), C.c_double(0.0)
+    check(lib().orc_last_cg_stats(C.byref(its), C.byref(beta0), C.byref(res), C.byref(ev)))
+    return its.value, beta0.value, res.value, ev.value
+
+
 def csr_spmv(a, x, reps=1):
     """y = A x on the device; returns (y, avg_ms_per_launch)."""
     a = a.tocsr()

@@ -44,6 +44,7 @@ class SolutionMethod:  # lib.rs:171-179 (+ new-build extensions)
     GaussSeidel, Jacobi, Multigrid, BiCGSTAB = range(4)
     MulticolorGS, BiCGSTAB_GS, Multigrid_GS = 16, 17, 18
     GMRES = 19
+    CG = 20  # preconditioned conjugate gradients: symmetric positive definite systems (the pressure correction)
 
 
 class ReductionOrder:  # include/orc_types.h OrcReductionOrder
@@ -56,6 +57,14 @@ class PreconditionMethod:  # lib.rs:181-185
 
 class FaceConditionTypes:  # mesh.rs:25-65
     Interior, Wall, PressureInlet, PressureOutlet, Symmetry, VelocityInlet = 2, 3, 4, 5, 7, 10
+
+
+class LinearSolver(C.Structure):
+    """OrcLinearSolver: a linear solver of its own for one system (Solver.set_pressure_solver)."""
+    _fields_ = [
+        ("solver_type", C.c_int32), ("preconditioner", C.c_int32), ("iterations", C.c_uint64),
+        ("relative_convergence_threshold", C.c_double), ("relaxation", C.c_double),
+    ]
 
 
 class TimeScheme:  # include/orc_types.h OrcTimeScheme

@@ -125,6 +125,33 @@ class Solver:
             return rep if report else st
         return (st, rep) if report else st
 
+    # ---------------------------------------------------------------- a linear solver of its own for p' (orc_solver_set_pressure_solver)
+    def set_pressure_solver(self, solver_type=None, preconditioner=1, iterations=50, threshold=0.0, relaxation=0.5, raise_on_error=True):
+        """the p' solves run with these five fields instead of the settings' (settings.SolutionMethod.CG: the pressure correction
+        is symmetric positive definite); solver_type=None removes the override"""
+        if solver_type is None:
+            st = lib().orc_solver_set_pressure_solver(self.ptr, None)
+        else:
+            from .settings import LinearSolver
+            c = LinearSolver(solver_type=int(solver_type), preconditioner=int(preconditioner), iterations=int(iterations),
+                             relative_convergence_threshold=float(threshold), relaxation=float(relaxation))
+            st = lib().orc_solver_set_pressure_solver(self.ptr, C.byref(c))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def pressure_solver(self):
+        """(enabled, dict of the five fields the p' solve runs with: the override's, or the settings' when none is set)"""
+        from .settings import LinearSolver
+        c, on = LinearSolver(), C.c_int32(0)
+        check(lib().orc_solver_get_pressure_solver(self.ptr, C.byref(c), C.byref(on)))
+        return bool(on.value), dict(solver_type=c.solver_type, preconditioner=c.preconditioner, iterations=c.iterations,
+                                    threshold=c.relative_convergence_threshold, relaxation=c.relaxation)
+
+    def debug_pressure_hierarchies(self):
+        """test hook: p' Multigrid hierarchies this solver has set up so far (ahead of a solve or inside one)"""
+        return int(lib().orc_solver_debug_pressure_hierarchies(self.ptr))
+
     # ---------------------------------------------------------------- passive scalar (orc_solver_set_scalar)
     def set_scalar(self, settings=None, raise_on_error=True):
         """a settings.ScalarSettings turns the scalar arm on (phi = 0, no source, no levels, every zone DEFAULT); None turns it off"""
