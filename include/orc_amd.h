@@ -461,7 +461,7 @@ int orc_debug_xwin_counters(long long out[3], int reset);
  * SIMPLE iteration share their pattern; when v's and w's fine pairings verify as u's, ONE symbolic pass carries the three value sets:
  * linear_algebra.rs:80-84 per system, bit-identical).  ORC_AMG_SHARED_GALERKIN=0 switches the shared pass off. */
 long long orc_debug_shared_galerkin(int reset);
-/* Test hook: product launches per kernel family since the last reset.  launch_spmv (orc_amd/csrc/linalg.hip) picks one of about a
+/* Test hook: product launches per kernel family since the last reset.  launch_spmv (orc_amd/csrc/spmv.hip) picks one of about a
  * dozen instantiations by the matrix (raggedness class, narrow column image, mirrors) and by the call (scalings carried or materialised,
  * non-temporal policy); the counters are incremented on the host where each launch is made, so a test that compares a product bit for
  * bit can tell which kernel produced the bits.  out[f] for f < min(n_out, ORC_PRODUCT_FAMILIES) (further entries are zeroed); out may

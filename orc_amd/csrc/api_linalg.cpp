@@ -4,12 +4,6 @@
 #include "linalg.hpp"
 
 namespace orc {
-int amg_debug_coarsen(const MatView &A, Arena &arena, std::vector<int> &choice_h, std::vector<int64_t> &row_ptr_h,
-                      std::vector<int64_t> &col_h, std::vector<double> &val_h, int *rounds, const double *x_h = nullptr, double *y_h = nullptr,
-                      int scaled = 0, int *mirror_out = nullptr);
-int amg_debug_packed(const MatView &A, Arena &arena, int64_t sizes[5], int32_t *row_len_h, int64_t *pk_ptr_h, int32_t *pk_col_h, double *pk_val_h,
-                     int64_t *lptr_h, uint16_t *lidx_h, int32_t *wcol_h, int32_t *wsize_h);
-int gs_debug_coloring(const SellDev &P, std::vector<int> &colors, int *n_colors);
 static SolveStats g_last_stats;
 SolveStats &last_stats() { return g_last_stats; }
 }  // namespace orc

@@ -9,10 +9,6 @@
 
 using namespace orc;
 
-namespace orc {
-void gs_forget_pattern(const void *col_ptr);  // gs.hip
-}
-
 namespace {
 
 int upload_csr_values(OrcMesh &m, const double *host_vals, DevBuf<double> &sell, DevBuf<double> &tmp) {
@@ -27,11 +23,6 @@ int download_csr_values(OrcMesh &m, const DevBuf<double> &sell, double *host_val
 }
 
 }  // namespace
-
-namespace orc {
-int bench_gs_sweep_dev(const MatView &A, const double *b, double *x, int reps, Arena &arena, float *ms_per_sweep, int *n_colors);  // gs.hip
-int bench_gs_sweep0_dev(const MatView A[3], const double *const b[3], int reps, Arena &arena, float ms[2], int *n_colors);         // gs.hip
-}
 
 extern "C" {
 

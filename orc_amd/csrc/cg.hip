@@ -9,7 +9,7 @@
 // destroys symmetry; this arm is dispatched ahead of that block and applies M = D inside the recurrence: z = dinv * r.
 //
 // One iteration (n rows, 8-byte values):
-//   product     q = A p, partial sums of p.q                          launch_spmv with EpiStoreDot (cg_product_dev), halo as every arm
+//   product     q = A p, partial sums of p.q                          product_store_dot (spmv.hip), halo as every arm
 //   cg_update_k folds p.q; alpha = rho / p.q; x += alpha p; r -= alpha q; z = dinv r; partial sums of r.z and r.r
 //               reads x, p, r, q, dinv, writes x, r: 56 n bytes (48 n without a preconditioner)
 //   cg_direction_k folds r.z and r.r; stop test; beta = rho' / rho; p = z + beta p
@@ -31,12 +31,6 @@
 #include "linalg_kernels.hpp"
 
 namespace orc {
-
-int reduce_partials(const double *partials, int count, int nq, double *out, bool global);  // linalg.hip
-int gmres_residual_dev(const MatView &A, const double *b, const double *x, double *r, double *partials, int *grid,
-                       const double *skip_flags);  // linalg.hip: r = b - A x, partial sums of |r|^2
-int cg_product_dev(const MatView &A, const double *p, double *q, double *partials, int *grid, const double *skip_flags);  // linalg.hip
-SolveStats &last_stats();  // api_linalg.cpp
 
 // control block (device doubles)
 enum {
@@ -233,14 +227,14 @@ int cg_dev(const MatView &A, const double *b, double *x, uint64_t iteration_coun
     const int g_vec = grid_for((n + 1) / 2);  // two elements per lane
     if (jacobi) hipLaunchKernelGGL(cg_diag_inverse_k, dim3(grid_for(n)), dim3(kBlock), 0, s, A, dinv, st, status);
     int g = 0;
-    ORC_TRY(gmres_residual_dev(A, b, x, r, partials, &g, skip));  // r = b - A x, partial |r|^2
+    ORC_TRY(product_residual_norm(A, x, b, r, partials, &g, skip));  // r = b - A x, partial |r|^2
     ORC_TRY(reduce_partials(partials, g, 1, st + C_RR, global));
     hipLaunchKernelGGL(cg_begin_k, dim3(1), dim3(1), 0, s, st, st + C_RR);
     hipLaunchKernelGGL(cg_start_k, dim3(g_vec), dim3(kBlock), 0, s, r, dinv, p, n, partials);
     ORC_TRY(reduce_partials(partials, g_vec, 1, st + C_RHO0, global));
     for (uint64_t it = 0; it < iteration_count; ++it) {
         const int cur = C_RHO0 + (int)(it & 1), nxt = C_RHO0 + (int)((it & 1) ^ 1);
-        ORC_TRY(cg_product_dev(A, p, q, pq_partials, &g, skip));
+        ORC_TRY(product_store_dot(A, p, q, pq_partials, &g, skip));
         if (global) ORC_TRY(reduce_partials(pq_partials, g, 1, st + C_PQ, true));
         hipLaunchKernelGGL(cg_update_k, dim3(g_vec), dim3(kBlock), 0, s, st, cur, x, p, r, q, dinv, n, partials,
                            global ? (const double *)nullptr : (const double *)pq_partials, g);

@@ -26,7 +26,7 @@ struct Config {
     bool amg_shared_galerkin = true;    // ORC_AMG_SHARED_GALERKIN: one symbolic Galerkin pass for u, v, w when their pairings agree
     bool amg_l0_mirror = true;          // ORC_AMG_L0_MIRROR: row-contiguous mirror of the fine level for the set-up's row walks
     std::string galerkin_groups;        // ORC_GALERKIN_GROUPS: lanes per coarse row by tier, "16,16,32,64" (test hook: every merge width)
-    // ---- products (linalg.hip)
+    // ---- products (spmv.hip)
     int spmv_nt = -1;                   // ORC_SPMV_NT: non-temporal matrix loads 0 never / 1 always / -1 above 128 MB of stream
     bool spmv_narrow_cols = true;       // ORC_SPMV_NARROW_COLS: 16-bit column offsets on levels 0-1
     int materialize_scaling = 4;        // ORC_MATERIALIZE_SCALING: BiCGSTAB iterations from which a solve materialises its Jacobi-scaled values (0: never)

@@ -2,7 +2,7 @@
 // lib.rs:170).  Semantics: include/orc_amd.h at orc_set_gmres_restart; numpy restatement: tests/gmres_restatement.py.
 //
 // One Arnoldi step j (w = v_{j+1} slot of the basis, nq = j + 1 basis vectors before it):
-//   product     w = A v_j                                   launch_spmv (gmres_product_dev), scalings / halo as every arm
+//   product     w = A v_j                                   product_store (spmv.hip), scalings / halo as every arm
 //   dots        h1 = V^T w                                  gmres_dots_k          reads V (nq) + w         (j + 2) 8n bytes
 //   update+dots w -= V h1 ; h2 = V^T w                      gmres_update_dots_k   reads V + w, writes w    (j + 3) 8n bytes
 //   update+norm w -= V h2 ; |w|^2                           gmres_update_norm_k   reads V + w, writes w    (j + 3) 8n bytes
@@ -23,11 +23,6 @@
 #include "linalg.hpp"
 
 namespace orc {
-
-int reduce_partials(const double *partials, int count, int nq, double *out, bool global);  // linalg.hip
-int gmres_product_dev(const MatView &A, const double *x, double *y, const double *skip_flags);  // linalg.hip
-int gmres_residual_dev(const MatView &A, const double *b, const double *x, double *r, double *partials, int *grid,
-                       const double *skip_flags);  // linalg.hip
 
 constexpr int kGmresMaxRestart = 64;
 constexpr int kGmresDefaultRestart = 30;
@@ -326,14 +321,14 @@ int gmres_dev(const MatView &A_in, const double *b, double *x, uint64_t iteratio
         const int k = (int)std::min<uint64_t>((uint64_t)m, left);
         left -= (uint64_t)k;
         int gr = 0;
-        ORC_TRY(gmres_residual_dev(A, b, x, V, partials, &gr, skip_step));  // v_0 <- b - A x, partial |r|^2
+        ORC_TRY(product_residual_norm(A, x, b, V, partials, &gr, skip_step));  // v_0 <- b - A x, partial |r|^2
         ORC_TRY(reduce_partials(partials, gr, 1, nrm2, global));
         hipLaunchKernelGGL(gmres_cycle_k, dim3(1), dim3(1), 0, s, st, nrm2, g, m, guard);
         hipLaunchKernelGGL(gmres_scale_k, dim3(g_vec), dim3(kBlock), 0, s, V, st, n, skip_step);
         for (int j = 0; j < k; ++j) {
             const int nq = j + 1;
             double *vj = V + (size_t)j * ld, *w = V + (size_t)(j + 1) * ld;
-            ORC_TRY(gmres_product_dev(A, vj, w, skip_step));
+            ORC_TRY(product_store(A, vj, w, skip_step));
             hipLaunchKernelGGL(gmres_dots_k, dim3(g_dots), dim3(kBlock), 0, s, V, ld, nq, w, n, partials, skip_step);
             ORC_TRY(reduce_partials(partials, g_dots, nq, h1, global));
             const int tile = nq > 59 ? 64 : kGmresTile;

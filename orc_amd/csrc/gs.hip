@@ -522,7 +522,7 @@ static int get_coloring(const MatView &A, std::unique_ptr<Coloring> &owned, cons
     return ORC_OK;
 }
 
-// Right-preconditioned recurrences with the same breakdown guard as the reference arm (linalg.hip): scal[5] / scal[6]
+// Right-preconditioned recurrences with the same breakdown guard as the reference arm (bicgstab.hip): scal[5] / scal[6]
 // are the frozen flags (5: set by kernels that react with a no-op, 6: by the x/r update).
 __device__ __forceinline__ bool pre_frozen(const double *scal, int guard) { return guard && (scal[5] != 0. || scal[6] != 0.); }
 __device__ __forceinline__ bool fin_nz(double v) { return v != 0. && isfinite(v); }

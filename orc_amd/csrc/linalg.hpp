@@ -364,3 +364,5 @@ int vec_fill(double *x, double v, int64_t n);
 int vec_copy(double *dst, const double *src, int64_t n);
 
 }  // namespace orc
+
+#include "arms.hpp"

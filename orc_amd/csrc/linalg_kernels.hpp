@@ -1,4 +1,4 @@
-// linalg_kernels.hpp — device-side building blocks shared by linalg.hip and amg.hip.
+// linalg_kernels.hpp — device-side building blocks shared by the solver translation units (spmv.hip, bicgstab.hip, jacobi.hip, cg.hip, amg.hip, ...).
 #pragma once
 #include "linalg.hpp"
 
@@ -605,12 +605,5 @@ __global__ __launch_bounds__(kBlock) void spmv_xwin_k(MatView A, const double *_
         if (threadIdx.x == 0) partials[gridDim.x + blockIdx.x] = t;
     }
 }
-
-// Folds nq partial arrays of `count` entries each (fixed order => reproducible) into out[q].
-// One workgroup; launched after every kernel that produces partials.  In a multi-GPU run the
-// caller follows it with an RCCL all-reduce of out[0..nq).
-__global__ __launch_bounds__(1024) void reduce_partials_k(const double *__restrict__ partials, int count, int nq, double *__restrict__ out);
-
-int reduce_partials(const double *partials, int count, int nq, double *out, bool global = false);
 
 }  // namespace orc

@@ -3,14 +3,10 @@
 #include <cstdarg>
 #include <mutex>
 
-#include "common.hpp"
 #include "config.hpp"
+#include "linalg.hpp"
 
 namespace orc {
-void debug_amg_certification(long long out[2], bool reset);  // amg.hip
-long long debug_shared_galerkin(bool reset);                   // amg.hip
-int debug_xwin_counters(long long out[3], bool reset);       // amg.hip
-int debug_product_launches(long long *out, int n_out, bool reset);  // linalg.hip
 
 static thread_local Ctx *t_ctx_override = nullptr;
 

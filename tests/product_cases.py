@@ -1,6 +1,6 @@
 """Case table of the product-dispatch tests (tests/test_product_cases_cpu.py, tests/test_gpu_product_cases.py).
 
-launch_spmv (orc_amd/csrc/linalg.hip) picks a kernel by the matrix: the raggedness class of its SELL-64 image
+launch_spmv (orc_amd/csrc/spmv.hip) picks a kernel by the matrix: the raggedness class of its SELL-64 image
 (padded > 1.08 nnz ? (padded < 24 n ? 2 : 1) : 0), whether the all-or-nothing narrow column image exists (every slice and
 depth spans <= 65 535 columns), and by the call (scalings carried or materialised, non-temporal policy).  The matrices here sit
 on those thresholds and on the kernels' edges; every claim of the table (class, narrow kept / refused, which slice and depth is

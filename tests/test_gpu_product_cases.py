@@ -1,4 +1,4 @@
-"""Every product kernel a user matrix can select (launch_spmv, orc_amd/csrc/linalg.hip), at its boundaries, bit for bit.
+"""Every product kernel a user matrix can select (launch_spmv, orc_amd/csrc/spmv.hip), at its boundaries, bit for bit.
 
 The matrices are those of tests/product_cases.py: on the raggedness-class thresholds, on the 65 535 / 65 536 column span of the
 narrow image, with width-0 slices, empty rows, rows without a diagonal, last slices with one or two live rows and widths that
