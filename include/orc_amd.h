@@ -402,6 +402,26 @@ int orc_solver_last_scalar_report(OrcSolver *s, double report[4]);
 int orc_solver_assemble_scalar(OrcSolver *s, double *a, double *b);
 int orc_solver_scalar_boundary_flux(OrcSolver *s, double *per_zone);
 
+/* ---------- surface reports (new-build extension) ----------
+ * Force, moment, mass and momentum flow, area and area-weighted pressure of every boundary zone (orc_types.h OrcSurfaceQuantity;
+ * DESIGN.md §3 "Surface reports" has the definitions and the operator order).  Opt-in and read-only: two kernels over the boundary
+ * faces only, through an index the mesh builds on the device at its first report and keeps; zone types and values are read from the
+ * mesh's current zone table at report time.  Fixed association, no float atomics: the same state gives the same bits.  Interior
+ * zones and zones without owned faces give zeros; a boundary face in a zone whose type the assembly refuses (anything but Wall,
+ * VelocityInlet, PressureInlet, PressureOutlet, Symmetry) makes the call return ORC_ERR_UNSUPPORTED_BC.  All three entries look for a
+ * device first (ORC_ERR_NO_DEVICE without one, whatever the arguments); then a non-finite origin, a null solver / mesh / field /
+ * output, and for orc_surface_integrals a non-finite or non-positive rho or mu, are ORC_ERR_BAD_ARGUMENT. */
+/* per zone ORC_SURFACE_N doubles (orc_types.h OrcSurfaceQuantity), zone index as orc_mesh_update_zones uses it.
+ * origin: reference point of MOMENT, NULL = (0,0,0).  Uses the solver's current u, v, w, p, rho, mu and the mesh's
+ * current zone table; changes no bit of the solver.  On a partitioned mesh every rank calls it and receives the global sums. */
+int orc_solver_surface_report(OrcSolver *s, const double origin[3], double *per_zone /*[n_zones * ORC_SURFACE_N]*/);
+/* the same on host fields in ORC cell order (post-processing a read_data file): uploads, reports, frees */
+int orc_surface_integrals(OrcMesh *m, const double *u, const double *v, const double *w, const double *p,
+                          double rho, double mu, const double origin[3], double *per_zone);
+/* the boundary index (builds it if need be): zone_ptr[n_zones + 1]; faces (may be NULL) receives zone_ptr[n_zones] face ids
+ * in the mesh's internal face numbering; *n_builds = how often this mesh has built it (stays 1); *chunk = faces per workgroup */
+int orc_mesh_boundary_index(OrcMesh *m, int64_t *zone_ptr, int32_t *faces, int64_t *n_builds, int32_t *chunk);
+
 /* ---------- measurement hooks (bench.py): HIP-event timed launches of single kernels ---------- */
 /* y = A x with the momentum matrix a_u of the solver, `reps` launches; returns average ms per launch */
 int orc_bench_spmv(OrcSolver *s, int reps, double *avg_ms, double *checksum);

@@ -204,6 +204,23 @@ typedef struct OrcLinearSolver {
     double relaxation;
 } OrcLinearSolver;
 
+/* Per-zone surface reports (new-build extension; orc_amd.h: orc_solver_surface_report): every zone gets ORC_SURFACE_N doubles, each
+ * the sum over the zone's boundary faces of owned cells of the term named below.  n = unit normal out of the face's cell, A = area,
+ * U_f / p_f / phi_f = the boundary value of get_face_velocity (VelocityInterpolation::None) / get_face_pressure / get_face_flux,
+ * d_f = mu A / |x_f - x_P| on Wall and VelocityInlet faces and 0 elsewhere (the coefficient of build_momentum_diffusion_matrix).
+ * DESIGN.md §3 "Surface reports" fixes the operator order of every term. */
+enum OrcSurfaceQuantity {
+    ORC_SURFACE_AREA = 0,            /* A */
+    ORC_SURFACE_MASS_FLOW = 1,       /* rho phi_f A; positive = leaving the domain */
+    ORC_SURFACE_PRESSURE_FORCE = 2,  /* [2..4] p_f A n: the force the fluid exerts ON the boundary */
+    ORC_SURFACE_VISCOUS_FORCE = 5,   /* [5..7] d_f (U_P - U_f): likewise, the momentum the discrete equations hand to the boundary */
+    ORC_SURFACE_MOMENTUM_FLOW = 8,   /* [8..10] rho phi_f A U_f */
+    ORC_SURFACE_MOMENT = 11,         /* [11..13] (x_f - x_0) x (p_f A n + d_f (U_P - U_f)) about the caller's origin x_0 */
+    ORC_SURFACE_PRESSURE_AREA = 14,  /* p_f A; mean pressure = [14] / [0] */
+    ORC_SURFACE_FACES = 15,          /* 1.0 */
+    ORC_SURFACE_N = 16
+};
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,15 @@ def lib():
             L.orc_solver_get_pressure_solver.restype = C.c_int
             L.orc_solver_debug_pressure_hierarchies.argtypes = [C.c_void_p]
             L.orc_solver_debug_pressure_hierarchies.restype = C.c_longlong
+        # surface reports (orc_amd.h "surface reports"): full signatures
+        if hasattr(L, "orc_solver_surface_report"):
+            _f64, _i64, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+            L.orc_solver_surface_report.argtypes = [C.c_void_p, _f64, _f64]
+            L.orc_solver_surface_report.restype = C.c_int
+            L.orc_surface_integrals.argtypes = [C.c_void_p, _f64, _f64, _f64, _f64, C.c_double, C.c_double, _f64, _f64]
+            L.orc_surface_integrals.restype = C.c_int
+            L.orc_mesh_boundary_index.argtypes = [C.c_void_p, _i64, _i32, _i64, _i32]
+            L.orc_mesh_boundary_index.restype = C.c_int
         _lib = L
     return _lib
 

@@ -26,6 +26,19 @@ struct MeshDev {
     const double *zvec = nullptr;    // FaceZone.vector_value [3Z]
 };
 
+// The boundary faces of owned cells grouped by zone (surface.hip): built on the device at a mesh's first surface report and
+// never again — the face -> zone map of a mesh is immutable; zone types and values are read from ztype / zscal / zvec at
+// report time.  The report's partial sums, output and status word live here too, so that a report allocates nothing.
+struct SurfaceIndex {
+    int64_t n_bfaces = 0, n_chunks = 0, builds = 0;
+    std::vector<int64_t> h_zone_ptr;       // [Z + 1] into bface
+    DevBuf<int32_t> bface;                 // face ids, ascending inside a zone
+    DevBuf<int32_t> chunk;                 // [n_chunks][4] = {zone, begin, end, 0}: <= kSurfaceChunk faces of ONE zone each
+    DevBuf<int32_t> zone_chunk_ptr;        // [Z + 1] into the chunk table
+    DevBuf<double> partials, out;          // [n_chunks][16], [Z][16]
+    DevBuf<int> status;
+};
+
 #ifdef __HIPCC__
 // the TVD limiters of settings::MomentumDiscretization (lib.rs:107-118): momentum_k and the scalar arm's scalar_face_k
 __device__ __forceinline__ double psi_eval(int momentum, double r) {
@@ -60,6 +73,7 @@ struct OrcMesh {
     std::vector<int64_t> h_row_ptr, h_col;  // the same pattern in CSR (ORC order) for the C ABI
     std::vector<int64_t> h_global_ids;      // orc_mesh_create_reordered: ORC index of every internal cell (empty = identity);
                                             // orc_solver_set_fields / get_fields / orc_solve_steady permute through it
+    std::unique_ptr<orc::SurfaceIndex> surface;  // null until the first surface report (surface.hip)
     orc::MeshDev dev() const;
 };
 
@@ -212,6 +226,9 @@ int k_scalar_face_flux(SolverState &s);
 int solve_scalar_system(SolverState &s, const OrcSettings &t);
 // one scalar solve of orc_solver_advance (levels shifted first), the report kept in s.sc.report
 int scalar_step_dev(SolverState &s);
+// surface reports (surface.hip): per zone ORC_SURFACE_N sums of the device fields u, v, w, p (the mesh's internal cell order) to the host
+int surface_report_dev(OrcMesh &m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
+                       const double origin[3], double *per_zone);
 
 }  // namespace orc
 

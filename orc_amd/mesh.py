@@ -209,6 +209,17 @@ class Mesh:
         zt, zs, zv = _i32(a["zone_type"]), _f64(a["zone_scalar"]), _f64(a["zone_vector"])
         check(lib().orc_mesh_update_zones(self.ptr, zt.ctypes.data_as(_I32), zs.ctypes.data_as(_F64), zv.ctypes.data_as(_F64)))
 
+    def boundary_index(self):
+        """orc_mesh_boundary_index: the boundary faces of owned cells grouped by zone, as the surface reports walk them (built on
+        the device at first use, then kept) -> (zone_ptr[Z + 1], faces[zone_ptr[Z]] ascending inside a zone and in the mesh's
+        internal face numbering, n_builds, chunk = faces per workgroup of a report)"""
+        zp = np.zeros(len(self.arrays["zone_type"]) + 1, np.int64)
+        nb, chunk = C.c_int64(0), C.c_int32(0)
+        check(lib().orc_mesh_boundary_index(self.ptr, zp.ctypes.data_as(_I64), None, C.byref(nb), C.byref(chunk)))
+        faces = np.zeros(max(int(zp[-1]), 1), np.int32)
+        check(lib().orc_mesh_boundary_index(self.ptr, zp.ctypes.data_as(_I64), faces.ctypes.data_as(_I32), C.byref(nb), C.byref(chunk)))
+        return zp, faces[:int(zp[-1])], int(nb.value), int(chunk.value)
+
     def matrix_pattern(self):
         rp = np.empty(self.n_cells + 1, np.int64)
         ci = np.empty(self.nnz, np.int64)

@@ -67,6 +67,68 @@ def calculate_gradients(mesh, u, v, w, p, settings, velocity=True):
     return gp, gu
 
 
+_SURFACE_N = 16  # orc_types.h ORC_SURFACE_N
+
+
+class SurfaceReport:
+    """Per-zone surface sums (orc_solver_surface_report / orc_surface_integrals): `raw` is the (Z, 16) array in the order of
+    OrcSurfaceQuantity; the properties are views of it.  Forces and the moment are what the fluid exerts ON the boundary; a
+    positive mass flow leaves the domain."""
+
+    def __init__(self, raw, zone_names=None):
+        self.raw = np.asarray(raw, dtype=np.float64).reshape(-1, _SURFACE_N)
+        self.zone_names = list(zone_names) if zone_names is not None else None
+
+    area = property(lambda self: self.raw[:, 0])
+    mass_flow = property(lambda self: self.raw[:, 1])
+    pressure_force = property(lambda self: self.raw[:, 2:5])
+    viscous_force = property(lambda self: self.raw[:, 5:8])
+    momentum_flow = property(lambda self: self.raw[:, 8:11])
+    moment = property(lambda self: self.raw[:, 11:14])
+    faces = property(lambda self: self.raw[:, 15])
+
+    @property
+    def force(self):
+        """pressure plus viscous force, (Z, 3)"""
+        return self.raw[:, 2:5] + self.raw[:, 5:8]
+
+    @property
+    def mean_pressure(self):
+        """area-weighted mean of the face pressure; NaN where the zone has no area"""
+        a = self.raw[:, 0]
+        out = np.full(len(a), np.nan)
+        np.divide(self.raw[:, 14], a, out=out, where=a != 0.0)
+        return out
+
+    def zone(self, name):
+        """the 16 sums of the zone called `name` (needs a mesh whose arrays carry zone_names)"""
+        if self.zone_names is None:
+            raise KeyError("the mesh arrays carry no zone_names")
+        return self.raw[self.zone_names.index(name)]
+
+
+def _origin(origin):
+    if origin is None:
+        return None, None
+    o = _f64(origin).reshape(3)
+    return o, _p(o)
+
+
+def surface_integrals(mesh, u, v, w, p, rho, mu, origin=None, raise_on_error=True):
+    """orc_surface_integrals: the surface report of host fields in ORC cell order (with raise_on_error=False: (status, report))"""
+    u, v, w, p = map(_f64, (u, v, w, p))
+    for a in (u, v, w, p):
+        assert len(a) == mesh.n_cells
+    out = np.zeros((len(mesh.arrays["zone_type"]), _SURFACE_N))
+    keep, o = _origin(origin)
+    st = lib().orc_surface_integrals(mesh.ptr, _p(u), _p(v), _p(w), _p(p), C.c_double(rho), C.c_double(mu), o, _p(out))
+    rep = SurfaceReport(out, mesh.arrays.get("zone_names"))
+    if raise_on_error:
+        check(st)
+        return rep
+    return st, rep
+
+
 class Solver:
     """Device-resident state of one solve_steady call (OrcSolver*): what bench.py drives."""
 
@@ -219,6 +281,18 @@ class Solver:
         out = np.zeros(len(self.mesh.arrays["zone_type"]))
         check(lib().orc_solver_scalar_boundary_flux(self.ptr, _p(out)))
         return out
+
+    def surface_report(self, origin=None, raise_on_error=True):
+        """orc_solver_surface_report: per-zone force, moment, mass and momentum flow, area and mean pressure of the current
+        state -> SurfaceReport (with raise_on_error=False: (status, report)); reads only"""
+        out = np.zeros((len(self.mesh.arrays["zone_type"]), _SURFACE_N))
+        keep, o = _origin(origin)
+        st = lib().orc_solver_surface_report(self.ptr, o, _p(out))
+        rep = SurfaceReport(out, self.mesh.arrays.get("zone_names"))
+        if raise_on_error:
+            check(st)
+            return rep
+        return st, rep
 
     def assemble_momentum(self):
         nnz, n = self.mesh.nnz, self.n
