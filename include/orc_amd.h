@@ -476,6 +476,15 @@ long long orc_debug_collectives(int reset);
 int orc_debug_clamp_partials_grid(long long requested);
 int orc_debug_max_partials(void);
 int orc_debug_amg_certification(long long out[2], int reset);
+/* Test hook: what the calling process's most recent pairing (build_restriction_matrix, linear_algebra.rs:30-60) and the Galerkin product
+ * behind it did; not cumulative.  out[0..4] = the deferred-acceptance chains: rows left to them, their proposals, proposals found by a scan of
+ * the row (its four-entry preference list having run out), proposals of the longest chain, chains cut by the step budget (ORC_AMG_DA_STEPS);
+ * out[5] = rows the certifying pass would have paired differently; out[6] = sweeps of the slice-sequential fallback (0: it did not run, the
+ * chains' pairing was certified as it stood); out[7] = lanes per chain (0: ORC_AMG_DA=0, or a sibling's pairing was taken over);
+ * out[8..14] = coarse rows per LDS tier of the merge (tier t holds rows of at most 32 << t candidate entries; longer rows, which the set-up
+ * refuses, count in the last); out[15] = the largest candidate count.  Host-side copies of counters the set-up reads anyway: no device
+ * access, no synchronisation. */
+int orc_debug_amg_setup_stats(long long out[16], int reset);
 int orc_debug_xwin_counters(long long out[3], int reset);
 /* [r04] coarse operators of SIBLING systems built by a shared Galerkin pass since the last reset (the u, v, w momentum matrices of a
  * SIMPLE iteration share their pattern; when v's and w's fine pairings verify as u's, ONE symbolic pass carries the three value sets:

@@ -63,6 +63,10 @@ def lib():
             L.orc_surface_integrals.restype = C.c_int
             L.orc_mesh_boundary_index.argtypes = [C.c_void_p, _i64, _i32, _i64, _i32]
             L.orc_mesh_boundary_index.restype = C.c_int
+        # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
+        if hasattr(L, "orc_debug_amg_setup_stats"):
+            L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]
+            L.orc_debug_amg_setup_stats.restype = C.c_int
         _lib = L
     return _lib
 

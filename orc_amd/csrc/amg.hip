@@ -1503,6 +1503,28 @@ void debug_amg_certification(long long out[2], bool reset) {
     out[1] = g_cert_rounds.load(std::memory_order_relaxed);
     if (reset) { g_cert_aggregations.store(0); g_cert_rounds.store(0); }
 }
+// orc_debug_amg_setup_stats: what the newest aggregate() and the galerkin() behind it did, from the counters both already copy to the host (no
+// device read, no synchronisation of its own): [0..4] DaCounters list, steps, scans, longest, overflow; [5] agg_verify_k's `changed` after the
+// chains; [6] sweeps of the fallback (0: it did not run); [7] lanes per chain (0: no chains, ORC_AMG_DA=0); [8..14] coarse rows per LDS tier;
+// [15] the largest candidate count of a coarse row.  Not cumulative: aggregate() overwrites [0..7] and clears the rest, galerkin() fills [8..15].
+static std::mutex g_setup_stats_mu;
+static long long g_setup_stats[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static void note_aggregate_stats(const long long ag[8]) {
+    std::lock_guard<std::mutex> lk(g_setup_stats_mu);
+    for (int i = 0; i < 16; ++i) g_setup_stats[i] = i < 8 ? ag[i] : 0;
+}
+static void note_galerkin_stats(const int *htier, int max_cand) {
+    std::lock_guard<std::mutex> lk(g_setup_stats_mu);
+    for (int t = 0; t < 7; ++t) g_setup_stats[8 + t] = htier[t];
+    g_setup_stats[15] = max_cand;
+}
+void debug_amg_setup_stats(long long out[16], bool reset) {
+    std::lock_guard<std::mutex> lk(g_setup_stats_mu);
+    for (int i = 0; i < 16; ++i) {
+        out[i] = g_setup_stats[i];
+        if (reset) g_setup_stats[i] = 0;
+    }
+}
 int debug_xwin_counters(long long out[3], bool reset) {
     unsigned long long h[3] = {0, 0, 0};
     ORC_HIP(hipDeviceSynchronize());
@@ -1536,7 +1558,8 @@ static int aggregate(const MatView &A, Arena &arena, int *choice, int *chooser, 
     hipStream_t st = ctx().stream;
     const bool trace = cfg().amg_trace;
     ORC_HIP(hipMemsetAsync(C, 0, sizeof(AggCounters), st));
-    if (n == 0) { if (rounds_out) *rounds_out = 0; return ORC_OK; }
+    long long ag[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // orc_debug_amg_setup_stats [0..7]
+    if (n == 0) { note_aggregate_stats(ag); if (rounds_out) *rounds_out = 0; return ORC_OK; }
     auto finish_from_choice = [&]() -> int {
         ORC_HIP(hipMemsetAsync(chooser, 0xff, sizeof(int) * (size_t)n, st));
         hipLaunchKernelGGL(chooser_k, dim3(g), dim3(kBlock), 0, st, (const int *)choice, chooser, n);
@@ -1554,6 +1577,7 @@ static int aggregate(const MatView &A, Arena &arena, int *choice, int *chooser, 
         ORC_HIP(hipStreamSynchronize(st));
         if (trace) fprintf(stderr, "[amg sibling n=%lld] rows that would change: %d\n", (long long)n, hc.changed);
         if (hc.changed == 0) {
+            note_aggregate_stats(ag);
             if (rounds_out) *rounds_out = 1;
             return finish_from_choice();
         }
@@ -1590,7 +1614,9 @@ static int aggregate(const MatView &A, Arena &arena, int *choice, int *chooser, 
         ORC_HIP(hipStreamSynchronize(st));
         if (trace) fprintf(stderr, "[amg da n=%lld] rows left to the chains %d, their proposals %d (%d by a scan of the row), longest chain %d, chains cut %d, rows that would change %d\n",
                            (long long)n, hd.list, hd.steps, hd.scans, hd.longest, hd.overflow, hc.changed);
+        ag[0] = hd.list; ag[1] = hd.steps; ag[2] = hd.scans; ag[3] = hd.longest; ag[4] = hd.overflow; ag[5] = hc.changed; ag[7] = da_group == 4 || da_group == 8 ? da_group : 16;
         if (hd.overflow == 0 && hc.changed == 0) {
+            note_aggregate_stats(ag);
             g_cert_aggregations.fetch_add(1, std::memory_order_relaxed);  // certified by one pass that changed nothing
             g_cert_rounds.fetch_add(1, std::memory_order_relaxed);
             if (rounds_out) *rounds_out = 1;
@@ -1622,6 +1648,8 @@ static int aggregate(const MatView &A, Arena &arena, int *choice, int *chooser, 
     if (trace) fprintf(stderr, "[amg fallback n=%lld] %d sweeps\n", (long long)n, rounds);
     g_cert_aggregations.fetch_add(1, std::memory_order_relaxed);
     g_cert_rounds.fetch_add(rounds, std::memory_order_relaxed);
+    ag[6] = rounds;
+    note_aggregate_stats(ag);
     if (rounds_out) *rounds_out = rounds;
     return finish_from_choice();
 }
@@ -1747,6 +1775,7 @@ static int galerkin(const MatView &A, const int *choice, const int *chooser, Are
     ORC_HIP(hipMemcpyAsync(htier, tier_count, sizeof(htier), hipMemcpyDeviceToHost, st));
     ORC_HIP(hipStreamSynchronize(st));
     const int max_cand = std::max(hflags[0], 1);
+    note_galerkin_stats(htier, hflags[0]);
     const long long scratch_cap = (long long)std::max<unsigned long long>(2ull * hcount[1], 64ull);
     int *s_col;
     double *s_val;
@@ -1769,6 +1798,9 @@ static int galerkin(const MatView &A, const int *choice, const int *chooser, Are
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&galerkin_merge_k<64, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&galerkin_merge_k<64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&galerkin_merge_k<64, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        // (one system, narrow groups: only with ORC_GALERKIN_GROUPS — 16 lanes per row on tier 5, 32 on tier 6 keep 96 KB of lists per wavefront)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&galerkin_merge_k<32, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&galerkin_merge_k<16, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&galerkin_merge_k<32, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&galerkin_merge_k<32, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&galerkin_merge_k<16, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -60,6 +60,7 @@ SolveStats &last_stats();
 int debug_product_launches(long long *out, int n_out, bool reset);
 // counters and single set-up steps of the hierarchy (amg.hip)
 void debug_amg_certification(long long out[2], bool reset);
+void debug_amg_setup_stats(long long out[16], bool reset);
 long long debug_shared_galerkin(bool reset);
 int debug_xwin_counters(long long out[3], bool reset);
 int amg_debug_coarsen(const MatView &A, Arena &arena, std::vector<int> &choice_h, std::vector<int64_t> &row_ptr_h,

@@ -352,6 +352,11 @@ int orc_debug_amg_certification(long long out[2], int reset) {
     orc::debug_amg_certification(out, reset != 0);
     return ORC_OK;
 }
+int orc_debug_amg_setup_stats(long long out[16], int reset) {
+    if (!out) return orc::set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
+    orc::debug_amg_setup_stats(out, reset != 0);
+    return ORC_OK;
+}
 long long orc_debug_shared_galerkin(int reset) { return orc::debug_shared_galerkin(reset != 0); }
 int orc_debug_xwin_counters(long long out[3], int reset) {
     if (!out) return orc::set_error(ORC_ERR_BAD_ARGUMENT, "null argument");

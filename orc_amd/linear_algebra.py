@@ -201,6 +201,21 @@ def amg_certification(reset=False):
     return out[0], out[1]
 
 
+AMG_SETUP_FIELDS = ("list", "steps", "scans", "longest", "overflow", "changed", "fallback_sweeps", "lanes")  # include/orc_amd.h out[0..7]
+
+
+def amg_setup_stats(reset=False):
+    """Test hook: what the most recent pairing and Galerkin product of this process did (orc_debug_amg_setup_stats; not cumulative): the
+    fields above, `fallback` (did the slice-sequential sweeps run?), `tiers` (coarse rows per LDS tier, 7 entries) and `max_cand`"""
+    out = (C.c_longlong * 16)()
+    check(lib().orc_debug_amg_setup_stats(out, C.c_int(1 if reset else 0)))
+    d = dict(zip(AMG_SETUP_FIELDS, (int(v) for v in out[:8])))
+    d["fallback"] = 1 if d["fallback_sweeps"] > 0 else 0
+    d["tiers"] = [int(v) for v in out[8:15]]
+    d["max_cand"] = int(out[15])
+    return d
+
+
 PRODUCT_FAMILIES = ("ragged", "packed", "window", "generic_scaled", "wide", "narrow", "narrow_nt", "mesh")  # include/orc_amd.h ORC_PRODUCT_*
 
 
