@@ -422,6 +422,39 @@ int orc_surface_integrals(OrcMesh *m, const double *u, const double *v, const do
  * in the mesh's internal face numbering; *n_builds = how often this mesh has built it (stays 1); *chunk = faces per workgroup */
 int orc_mesh_boundary_index(OrcMesh *m, int64_t *zone_ptr, int32_t *faces, int64_t *n_builds, int32_t *chunk);
 
+/* ---------- derived fields, boundary-face maps and VTU export (new-build extension) ----------
+ * Opt-in and read-only post-processing of a velocity field where it lives (DESIGN.md §3 "Derived fields and boundary maps").  The
+ * compute entries look for a device first (ORC_ERR_NO_DEVICE without one, whatever the arguments); then a null pointer, mask == 0 or
+ * a mask bit at or above ORC_DERIVED_N / ORC_BOUNDARY_N is ORC_ERR_BAD_ARGUMENT.  No atomics but a status word: the same state gives
+ * the same bits. */
+/* Cell fields (orc_types.h OrcDerivedField) selected by `mask`, from the velocity gradient of the solver's settings
+ * (gradient_reconstruction: Green-Gauss or least squares, exactly orc_calculate_gradients' grad_u), never stored.  out: the
+ * selected fields in ascending enum order, field k of the selection at out[k * n + c]; n, the cell order and the ownership are
+ * orc_solver_get_fields' (ORC order also on a reordered mesh; on a partitioned mesh the rank's array length with the owned cells
+ * filled and zeros behind them, ghost velocities exchanged first).  A boundary face in a zone the assembly refuses:
+ * ORC_ERR_UNSUPPORTED_BC; a singular least-squares system: ORC_ERR_SINGULAR_MATRIX.  Changes no bit of the solver. */
+int orc_solver_derived_fields(OrcSolver *s, uint32_t mask, double *out /*[popcount(mask) * n]*/);
+/* the same on host fields in ORC cell order: uploads, computes, frees */
+int orc_derived_fields(OrcMesh *m, const double *u, const double *v, const double *w, const OrcSettings *settings, uint32_t mask,
+                       double *out);
+/* Boundary-face maps (orc_types.h OrcBoundaryField): one value per face of orc_mesh_boundary_index, in its order; field k of the
+ * selection at out[k * nb + i], nb = zone_ptr[n_zones].  Terms, argument checks and refused zone types are the surface report's. */
+int orc_solver_boundary_fields(OrcSolver *s, uint32_t mask, double *out /*[popcount(mask) * nb]*/);
+int orc_boundary_fields(OrcMesh *m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
+                        uint32_t mask, double *out);
+/* VTK XML UnstructuredGrid (.vtu, version 1.0, header_type UInt64, little endian); host only, no device needed.  Cells with four
+ * triangles are VTK_TETRA, with six quadrilaterals over eight nodes VTK_HEXAHEDRON, every other cell VTK_POLYHEDRON; only the
+ * points the file uses are written, renumbered ascending.  data[a]: components[a] * n_cells doubles, structure-of-arrays by
+ * component.  encoding 0: ASCII (%.17g, round-trips exactly); 1: appended raw.  ORC_ERR_IO when the file cannot be written,
+ * ORC_ERR_BAD_ARGUMENT for null or inconsistent arrays or an index out of range. */
+int orc_write_vtu(const char *path, int64_t n_points, const double *points /*[3V]*/, int64_t n_cells, const int64_t *cell_face_ptr,
+                  const int64_t *cell_faces, const int64_t *face_node_ptr, const int64_t *face_nodes, int32_t n_arrays,
+                  const char *const *names, const int32_t *components, const double *const *data, int32_t encoding);
+/* the faces face_ids[n_faces] as VTK_POLYGON cells (a boundary map); data[a]: components[a] * n_faces doubles */
+int orc_write_vtu_faces(const char *path, int64_t n_points, const double *points, int64_t n_faces, const int64_t *face_ids,
+                        const int64_t *face_node_ptr, const int64_t *face_nodes, int32_t n_arrays, const char *const *names,
+                        const int32_t *components, const double *const *data, int32_t encoding);
+
 /* ---------- measurement hooks (bench.py): HIP-event timed launches of single kernels ---------- */
 /* y = A x with the momentum matrix a_u of the solver, `reps` launches; returns average ms per launch */
 int orc_bench_spmv(OrcSolver *s, int reps, double *avg_ms, double *checksum);

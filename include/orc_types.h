@@ -221,6 +221,36 @@ enum OrcSurfaceQuantity {
     ORC_SURFACE_N = 16
 };
 
+/* Derived cell fields (new-build extension; orc_amd.h: orc_solver_derived_fields).  G = the velocity gradient of the settings'
+ * gradient_reconstruction, G[i][j] = d u_i / d x_j (row = velocity component, the layout of orc_calculate_gradients' grad_u);
+ * S_ij = (G_ij + G_ji) / 2, W_ij = (G_ij - G_ji) / 2.  A field is selected by bit (1 << value) of a mask.  DESIGN.md §3
+ * "Derived fields and boundary maps" fixes the operator order. */
+enum OrcDerivedField {
+    ORC_DERIVED_VORTICITY_X = 0,     /* G[2][1] - G[1][2] */
+    ORC_DERIVED_VORTICITY_Y = 1,     /* G[0][2] - G[2][0] */
+    ORC_DERIVED_VORTICITY_Z = 2,     /* G[1][0] - G[0][1] */
+    ORC_DERIVED_VORTICITY_MAG = 3,   /* sqrt((wx^2 + wy^2) + wz^2) */
+    ORC_DERIVED_STRAIN_RATE_MAG = 4, /* sqrt(2 SS), SS = ((G00^2 + G11^2) + G22^2) + 2 ((S01^2 + S02^2) + S12^2) */
+    ORC_DERIVED_Q_CRITERION = 5,     /* (OO - SS) / 2, OO = 2 ((W01^2 + W02^2) + W12^2) */
+    ORC_DERIVED_DIVERGENCE = 6,      /* (G00 + G11) + G22 */
+    ORC_DERIVED_CONVECTIVE_RATE = 7, /* (sum_f |U_f . n| A) / (2 V) in 1/s, U_f = the linear face value; times dt = the Courant number */
+    ORC_DERIVED_N = 8
+};
+
+/* Boundary-face maps (new-build extension; orc_amd.h: orc_solver_boundary_fields): one value per boundary face of an owned cell in
+ * the order of orc_mesh_boundary_index.  Every term is the surface report's (OrcSurfaceQuantity above), same operator order. */
+enum OrcBoundaryField {
+    ORC_BOUNDARY_PRESSURE = 0,   /* p_f */
+    ORC_BOUNDARY_TRACTION_X = 1, /* [1..3] d_f (U_P - U_f) / A: the report's viscous term per unit area; 0 where d_f is 0 */
+    ORC_BOUNDARY_TRACTION_Y = 2,
+    ORC_BOUNDARY_TRACTION_Z = 3,
+    ORC_BOUNDARY_SHEAR_MAG = 4,  /* |t - (t . n) n| */
+    ORC_BOUNDARY_Y_PLUS = 5,     /* rho sqrt(SHEAR_MAG / rho) |x_f - x_P| / mu */
+    ORC_BOUNDARY_MASS_FLUX = 6,  /* rho phi_f; positive = leaving the domain */
+    ORC_BOUNDARY_AREA = 7,       /* A */
+    ORC_BOUNDARY_N = 8
+};
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,22 @@ def lib():
             L.orc_surface_integrals.restype = C.c_int
             L.orc_mesh_boundary_index.argtypes = [C.c_void_p, _i64, _i32, _i64, _i32]
             L.orc_mesh_boundary_index.restype = C.c_int
+        # derived fields, boundary-face maps and the VTU writers (orc_amd.h "derived fields, boundary-face maps and VTU export")
+        if hasattr(L, "orc_solver_derived_fields"):
+            _f64, _i64, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+            L.orc_solver_derived_fields.argtypes = [C.c_void_p, C.c_uint32, _f64]
+            L.orc_solver_derived_fields.restype = C.c_int
+            L.orc_derived_fields.argtypes = [C.c_void_p, _f64, _f64, _f64, C.c_void_p, C.c_uint32, _f64]
+            L.orc_derived_fields.restype = C.c_int
+            L.orc_solver_boundary_fields.argtypes = [C.c_void_p, C.c_uint32, _f64]
+            L.orc_solver_boundary_fields.restype = C.c_int
+            L.orc_boundary_fields.argtypes = [C.c_void_p, _f64, _f64, _f64, _f64, C.c_double, C.c_double, C.c_uint32, _f64]
+            L.orc_boundary_fields.restype = C.c_int
+            _tables = [C.c_int32, C.POINTER(C.c_char_p), _i32, C.POINTER(_f64), C.c_int32]
+            L.orc_write_vtu.argtypes = [C.c_char_p, C.c_int64, _f64, C.c_int64, _i64, _i64, _i64, _i64] + _tables
+            L.orc_write_vtu.restype = C.c_int
+            L.orc_write_vtu_faces.argtypes = [C.c_char_p, C.c_int64, _f64, C.c_int64, _i64, _i64, _i64] + _tables
+            L.orc_write_vtu_faces.restype = C.c_int
         # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
         if hasattr(L, "orc_debug_amg_setup_stats"):
             L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]

@@ -18,32 +18,10 @@
 #include <thread>
 
 #include "assembly.hpp"
+#include "gradient_cell.hpp"
 #include "linalg_kernels.hpp"
 
 namespace orc {
-
-
-struct V3 {
-    double x, y, z;
-};
-__device__ __forceinline__ V3 mk(double x, double y, double z) { return {x, y, z}; }
-__device__ __forceinline__ V3 vadd(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 vneg(V3 a) { return {-a.x, -a.y, -a.z}; }
-__device__ __forceinline__ V3 vmuls(V3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }   // Vector * Float (lib.rs:479-492)
-__device__ __forceinline__ V3 vdivs(V3 a, double s) { return {a.x / s, a.y / s, a.z / s}; }
-__device__ __forceinline__ V3 vadds(V3 a, double s) { return {a.x + s, a.y + s, a.z + s}; }
-__device__ __forceinline__ double vdot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ double vnorm(V3 a) { return sqrt(a.x * a.x + a.y * a.y + a.z * a.z); }
-// Float * Vector (lib.rs:540-548): z := rhs.y * self when q1
-__device__ __forceinline__ V3 smulv(double s, V3 a, int q1) { return {a.x * s, a.y * s, (q1 ? a.y : a.z) * s}; }
-
-__device__ __forceinline__ V3 face_normal(const MeshDev &M, int f) { return mk(M.nx[f], M.ny[f], M.nz[f]); }
-__device__ __forceinline__ V3 cell_centroid(const MeshDev &M, int c) { return mk(M.ccx[c], M.ccy[c], M.ccz[c]); }
-__device__ __forceinline__ V3 face_centroid(const MeshDev &M, int f) { return mk(M.fcx[f], M.fcy[f], M.fcz[f]); }
-__device__ __forceinline__ V3 zone_vec(const MeshDev &M, int z) { return mk(M.zvec[3 * z], M.zvec[3 * z + 1], M.zvec[3 * z + 2]); }
-
-__device__ __forceinline__ void raise(int *status, int code) { atomicCAS(status, 0, code); }
 
 #define GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
@@ -144,10 +122,6 @@ __device__ __forceinline__ double face_pressure_linear(const MeshDev &M, const d
     return p[M.c0[f]];  // Symmetry | Wall | VelocityInlet
 }
 
-__device__ __forceinline__ bool bc_supported(int zt) {
-    return zt == ORC_BC_INTERIOR || zt == ORC_BC_WALL || zt == ORC_BC_SYMMETRY || zt == ORC_BC_VELOCITY_INLET ||
-           zt == ORC_BC_PRESSURE_INLET || zt == ORC_BC_PRESSURE_OUTLET;
-}
 
 // calculate_pressure_gradient, GreenGauss(CellBased) (solver.rs:883-900); returns (gx, gy, gy) under Q1
 __global__ void grad_p_k(MeshDev M, const double *__restrict__ p, double *__restrict__ gp, int q1, int *status) {
@@ -169,98 +143,22 @@ __global__ void grad_p_k(MeshDev M, const double *__restrict__ p, double *__rest
     }
 }
 
-// get_face_velocity(…, Linear) (solver.rs:952-987)
-__device__ __forceinline__ V3 face_velocity_linear(const MeshDev &M, const double *__restrict__ u, const double *__restrict__ v,
-                                                   const double *__restrict__ w, int f, int zt, int z) {
-    const int a = M.c0[f];
-    if (zt == ORC_BC_WALL || zt == ORC_BC_VELOCITY_INLET) return zone_vec(M, z);
-    if (zt == ORC_BC_INTERIOR) {
-        const int b = M.c1[f];
-        return vdivs(vadd(mk(u[a], v[a], w[a]), mk(u[b], v[b], w[b])), 2.);
-    }
-    return mk(u[a], v[a], w[a]);
-}
 
-// calculate_velocity_gradient, GreenGauss arm (solver.rs:784-801): row = velocity component
+// calculate_velocity_gradient, GreenGauss arm (solver.rs:784-801): row = velocity component; the per-cell body is
+// grad_u_gg_cell (gradient_cell.hpp), shared with derived_cell_k
 __global__ void grad_u_k(MeshDev M, const double *__restrict__ u, const double *__restrict__ v, const double *__restrict__ w,
                          double *__restrict__ gu, int *status) {
     const int64_t n = M.n_cells;
     GRID_STRIDE(c, M.n_own) {
-        const double vol = M.vol[c];
-        V3 tx = mk(0., 0., 0.), ty = tx, tz = tx;
-        for (int q = M.cfp[c]; q < M.cfp[c + 1]; ++q) {
-            const int f = M.cf[q];
-            const int z = M.fzone[f];
-            const int zt = M.ztype[z];
-            if (!bc_supported(zt)) { raise(status, ORC_ERR_UNSUPPORTED_BC); continue; }  // solver.rs:1001
-            const V3 fv = face_velocity_linear(M, u, v, w, f, zt, z);
-            V3 nrm = face_normal(M, f);
-            if (M.c0[f] != c) nrm = vneg(nrm);
-            const V3 nn = vmuls(nrm, M.area[f] / vol);  // :799
-            tx = vadd(tx, mk(fv.x * nn.x, fv.x * nn.y, fv.x * nn.z));  // outer (lib.rs:275-293)
-            ty = vadd(ty, mk(fv.y * nn.x, fv.y * nn.y, fv.y * nn.z));
-            tz = vadd(tz, mk(fv.z * nn.x, fv.z * nn.y, fv.z * nn.z));
-        }
+        V3 tx, ty, tz;
+        double conv;
+        grad_u_gg_cell<false>(M, u, v, w, c, status, tx, ty, tz, conv);
         gu[0 * n + c] = tx.x; gu[1 * n + c] = tx.y; gu[2 * n + c] = tx.z;
         gu[3 * n + c] = ty.x; gu[4 * n + c] = ty.y; gu[5 * n + c] = ty.z;
         gu[6 * n + c] = tz.x; gu[7 * n + c] = tz.y; gu[8 * n + c] = tz.z;
     }
 }
 
-// ------------------------------------------------------------------ least-squares gradients (solver.rs:803-869, 903-947)
-// One thread per cell: the rows of the n x 3 system are the cell's faces in Cell.face_indices order — neighbour centroid
-// minus cell centroid with the value DIFFERENCE on interior faces, face centroid minus cell centroid with the face VALUE
-// itself on boundary faces (the reference's own formulation, solver.rs:830-838, 925-934) — and the normal equations are
-// accumulated face by face in nalgebra's small-matrix product order (one gemv per output column: left-to-right sums,
-// the first term assigned, (1 * a) * b per term), inverted with its closed 3 x 3 form (linalg/inverse.rs) and applied
-// by one more gemv.  A zero determinant is the reference's `try_inverse().unwrap()` panic.
-struct Lsq3 {
-    double ata[3][3], atb[3][3];
-    bool first = true;
-    __device__ __forceinline__ void add_row(const double x[3], const double *b, int nb) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const double t = (1. * x[i]) * x[j];
-                ata[i][j] = first ? t : t + 1. * ata[i][j];
-            }
-            for (int q = 0; q < nb; ++q) {
-                const double t = (1. * x[i]) * b[q];
-                atb[q][i] = first ? t : t + 1. * atb[q][i];
-            }
-        }
-        first = false;
-    }
-};
-// nalgebra try_inverse, dimension 3, in place; false = singular
-__device__ __forceinline__ bool inverse3(double a[3][3]) {
-    const double m11 = a[0][0], m12 = a[0][1], m13 = a[0][2], m21 = a[1][0], m22 = a[1][1], m23 = a[1][2], m31 = a[2][0], m32 = a[2][1], m33 = a[2][2];
-    const double minor_m12_m23 = m22 * m33 - m32 * m23;
-    const double minor_m11_m23 = m21 * m33 - m31 * m23;
-    const double minor_m11_m22 = m21 * m32 - m31 * m22;
-    const double determinant = m11 * minor_m12_m23 - m12 * minor_m11_m23 + m13 * minor_m11_m22;
-    if (determinant == 0.) return false;
-    a[0][0] = minor_m12_m23 / determinant;
-    a[0][1] = (m13 * m32 - m33 * m12) / determinant;
-    a[0][2] = (m12 * m23 - m22 * m13) / determinant;
-    a[1][0] = -minor_m11_m23 / determinant;
-    a[1][1] = (m11 * m33 - m31 * m13) / determinant;
-    a[1][2] = (m13 * m21 - m23 * m11) / determinant;
-    a[2][0] = minor_m11_m22 / determinant;
-    a[2][1] = (m12 * m31 - m32 * m11) / determinant;
-    a[2][2] = (m11 * m22 - m21 * m12) / determinant;
-    return true;
-}
-__device__ __forceinline__ void inv_times3(const double ainv[3][3], const double b[3], double out[3]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        double y = (1. * ainv[i][0]) * b[0];
-        y = (1. * ainv[i][1]) * b[1] + 1. * y;
-        y = (1. * ainv[i][2]) * b[2] + 1. * y;
-        out[i] = y;
-    }
-}
 
 __global__ void grad_p_lsq_k(MeshDev M, const double *__restrict__ p, double *__restrict__ gp, int *status) {
     const int64_t n = M.n_cells;
@@ -296,35 +194,8 @@ __global__ void grad_u_lsq_k(MeshDev M, const double *__restrict__ u, const doub
                              double *__restrict__ gu, int *status) {
     const int64_t n = M.n_cells;
     GRID_STRIDE(c, M.n_own) {
-        const V3 cc = cell_centroid(M, (int)c);
-        Lsq3 L;
-        for (int q = M.cfp[c]; q < M.cfp[c + 1]; ++q) {
-            const int f = M.cf[q];
-            const int z = M.fzone[f];
-            const int zt = M.ztype[z];
-            if (!bc_supported(zt)) { raise(status, ORC_ERR_UNSUPPORTED_BC); continue; }
-            V3 d;
-            double b[3];
-            if (zt == ORC_BC_INTERIOR) {
-                const int nb = (M.c0[f] == c) ? M.c1[f] : M.c0[f];
-                d = vsub(cell_centroid(M, nb), cc);
-                b[0] = u[nb] - u[c]; b[1] = v[nb] - v[c]; b[2] = w[nb] - w[c];
-            } else {  // get_face_velocity(…, None): zone vector on walls / velocity inlets, cell-0 velocity elsewhere
-                d = vsub(face_centroid(M, f), cc);
-                const int a0 = M.c0[f];
-                const V3 fv = (zt == ORC_BC_WALL || zt == ORC_BC_VELOCITY_INLET) ? zone_vec(M, z) : mk(u[a0], v[a0], w[a0]);
-                b[0] = fv.x; b[1] = fv.y; b[2] = fv.z;
-            }
-            const double x[3] = {d.x, d.y, d.z};
-            L.add_row(x, b, 3);
-        }
-        double g[3][3] = {{0., 0., 0.}, {0., 0., 0.}, {0., 0., 0.}};
-        if (L.first || !inverse3(L.ata)) raise(status, ORC_ERR_SINGULAR_MATRIX);
-        else {
-            inv_times3(L.ata, L.atb[0], g[0]);
-            inv_times3(L.ata, L.atb[1], g[1]);
-            inv_times3(L.ata, L.atb[2], g[2]);
-        }
+        double g[3][3], conv;
+        grad_u_lsq_cell<false>(M, u, v, w, c, status, g, conv);
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll

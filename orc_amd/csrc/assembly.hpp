@@ -229,6 +229,8 @@ int scalar_step_dev(SolverState &s);
 // surface reports (surface.hip): per zone ORC_SURFACE_N sums of the device fields u, v, w, p (the mesh's internal cell order) to the host
 int surface_report_dev(OrcMesh &m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
                        const double origin[3], double *per_zone);
+// the boundary index of the mesh (m.surface), built at first use: what the reports and the boundary maps of derived.hip walk
+int surface_index(OrcMesh &m);
 
 }  // namespace orc
 

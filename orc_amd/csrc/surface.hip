@@ -275,6 +275,8 @@ bool finite3(const double *x) { return std::isfinite(x[0]) && std::isfinite(x[1]
 
 }  // namespace
 
+int surface_index(OrcMesh &m) { return ensure_index(m); }
+
 int surface_report_dev(OrcMesh &m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
                        const double origin[3], double *per_zone) {
     ORC_TRY(ensure_index(m));

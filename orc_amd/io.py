@@ -130,3 +130,52 @@ def write_gradients(mesh, cell_centroid, u, v, w, p, output_file_name, decimal_p
     u, v, w, p = (np.ascontiguousarray(x, np.float64) for x in (u, v, w, p))
     check(lib().orc_write_gradients(mesh.ptr, _p(cc), _p(u), _p(v), _p(w), _p(p), str(output_file_name).encode(),
                                     C.c_int(int(decimal_precision)), C.byref(settings)))
+
+
+# ------------------------------------------------------------------ VTK XML export (orc_write_vtu, orc_write_vtu_faces)
+def _vtu_tables(arrays, n_items):
+    """{name: ndarray[n] or [n, k]} -> (keep-alive list, n_arrays, names, components, data) of the C tables (SoA by component)"""
+    names, comps, cols = [], [], []
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim == 1:
+            a = a[:, None]
+        if a.ndim != 2 or a.shape[0] != n_items:
+            raise ValueError("array '%s' has shape %s, expected (%d,) or (%d, k)" % (name, a.shape, n_items, n_items))
+        names.append(str(name).encode())
+        comps.append(a.shape[1])
+        cols.append(np.ascontiguousarray(a.T))  # component-major
+    k = len(names)
+    c_names = (C.c_char_p * max(k, 1))(*names)
+    c_comps = np.array(comps if comps else [0], np.int32)
+    c_data = (_F64 * max(k, 1))(*[_p(c) for c in cols])
+    return (cols, c_comps), k, c_names, _p(c_comps, _I32), c_data
+
+
+_ENCODINGS = {"ascii": 0, "raw": 1}
+
+
+def write_vtu(path, mesh_data, cell_arrays, encoding="raw"):
+    """orc_write_vtu: the cells of `mesh_data` (a MeshData: nodes and connectivity) with `cell_arrays` {name: ndarray[n] or [n, k]}
+    in ORC cell order as a VTK XML UnstructuredGrid; encoding "raw" (appended binary) or "ascii" (both round-trip exactly)."""
+    vert, fnp, fn = mesh_data.nodes()
+    a = mesh_data.arrays()
+    cfp, cf = np.ascontiguousarray(a["cell_face_ptr"], np.int64), np.ascontiguousarray(a["cell_faces"], np.int64)
+    keep, k, names, comps, data = _vtu_tables(cell_arrays, mesh_data.n_cells)
+    check(lib().orc_write_vtu(str(path).encode(), C.c_int64(len(vert)), _p(vert), C.c_int64(mesh_data.n_cells), _p(cfp, _I64), _p(cf, _I64),
+                              _p(fnp, _I64), _p(fn, _I64), C.c_int32(k), names, comps, data, C.c_int32(_ENCODINGS[encoding])))
+
+
+def write_vtu_boundary(path, mesh_data, boundary_fields, extra_arrays=None, encoding="raw"):
+    """orc_write_vtu_faces: the faces of a solver.BoundaryFields as VTK_POLYGON cells carrying its arrays, a per-face "zone" index
+    and `extra_arrays` {name: ndarray[nb] or [nb, k]}.  The traction components are also written as one 3-vector "traction"."""
+    vert, fnp, fn = mesh_data.nodes()
+    faces = np.ascontiguousarray(boundary_fields.faces, np.int64)
+    arrays = dict(boundary_fields.arrays)
+    if all(("traction_" + c) in arrays for c in "xyz"):
+        arrays["traction"] = np.stack([arrays["traction_" + c] for c in "xyz"], axis=1)
+    arrays["zone"] = np.repeat(np.arange(len(boundary_fields.zone_ptr) - 1), np.diff(boundary_fields.zone_ptr)).astype(np.float64)
+    arrays.update(extra_arrays or {})
+    keep, k, names, comps, data = _vtu_tables(arrays, len(faces))
+    check(lib().orc_write_vtu_faces(str(path).encode(), C.c_int64(len(vert)), _p(vert), C.c_int64(len(faces)), _p(faces, _I64), _p(fnp, _I64),
+                                    _p(fn, _I64), C.c_int32(k), names, comps, data, C.c_int32(_ENCODINGS[encoding])))

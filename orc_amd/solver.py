@@ -129,6 +129,98 @@ def surface_integrals(mesh, u, v, w, p, rho, mu, origin=None, raise_on_error=Tru
     return st, rep
 
 
+# ------------------------------------------------------------------ derived fields and boundary-face maps (orc_types.h)
+DERIVED_NAMES = ("vorticity_x", "vorticity_y", "vorticity_z", "vorticity_mag", "strain_rate_mag", "q_criterion", "divergence",
+                 "convective_rate")  # OrcDerivedField, by value
+BOUNDARY_NAMES = ("pressure", "traction_x", "traction_y", "traction_z", "shear_mag", "y_plus", "mass_flux", "area")  # OrcBoundaryField
+
+
+def _mask_of(names_or_mask, table, groups=()):
+    """(mask, the names asked for) of a bit mask, one name or a list of names; `groups` maps a name to several fields"""
+    if isinstance(names_or_mask, (int, np.integer)):
+        mask = int(names_or_mask)
+        return mask, [n for k, n in enumerate(table) if mask >> k & 1]
+    names = [names_or_mask] if isinstance(names_or_mask, str) else list(names_or_mask)
+    mask = 0
+    for name in names:
+        for part in dict(groups).get(name, (name,)):
+            if part not in table:
+                raise KeyError("unknown field '%s'; known: %s" % (name, ", ".join(table + tuple(dict(groups)))))
+            mask |= 1 << table.index(part)
+    return mask, names
+
+
+_VORTICITY = (("vorticity", ("vorticity_x", "vorticity_y", "vorticity_z")),)
+
+
+def _derived_dict(out, mask, names, n):
+    """the SoA block of the selected fields -> {name: ndarray[n]}, 'vorticity' -> (n, 3)"""
+    rows = {DERIVED_NAMES[k]: out[i] for i, k in enumerate(k for k in range(len(DERIVED_NAMES)) if mask >> k & 1)}
+    res = {}
+    for name in names:
+        res[name] = np.stack([rows[c] for c in _VORTICITY[0][1]], axis=1) if name == "vorticity" else rows[name]
+    return res
+
+
+def derived_fields(mesh, u, v, w, settings, names, raise_on_error=True):
+    """orc_derived_fields: derived cell fields (DERIVED_NAMES, 'vorticity' = (n, 3), or a bit mask) of host fields in ORC cell
+    order, from the velocity gradient of settings.gradient_reconstruction -> {name: ndarray} (raise_on_error=False: (status, dict))"""
+    u, v, w = map(_f64, (u, v, w))
+    for a in (u, v, w):
+        assert len(a) == mesh.n_cells
+    mask, names = _mask_of(names, DERIVED_NAMES, _VORTICITY)
+    out = np.zeros((max(bin(mask).count("1"), 1), mesh.n_cells))
+    st = lib().orc_derived_fields(mesh.ptr, _p(u), _p(v), _p(w), C.byref(settings), C.c_uint32(mask & 0xFFFFFFFF), _p(out))
+    if raise_on_error:
+        check(st)
+        return _derived_dict(out, mask, names, mesh.n_cells)
+    return st, (_derived_dict(out, mask, names, mesh.n_cells) if st == 0 else {})
+
+
+class BoundaryFields:
+    """Boundary-face maps (orc_solver_boundary_fields / orc_boundary_fields): one value per boundary face of an owned cell in the
+    order of Mesh.boundary_index() — `zone_ptr` [Z + 1], `faces` (internal face numbering), `arrays` {name: ndarray[nb]}."""
+
+    def __init__(self, zone_ptr, faces, arrays, zone_names=None):
+        self.zone_ptr, self.faces, self.arrays = zone_ptr, faces, arrays
+        self.zone_names = list(zone_names) if zone_names is not None else None
+
+    def __getitem__(self, name):
+        return self.arrays[name]
+
+    def zone(self, name):
+        """{field: the slice of the zone called `name` (or with index `name`)}"""
+        if isinstance(name, str):
+            if self.zone_names is None:
+                raise KeyError("the mesh arrays carry no zone_names")
+            name = self.zone_names.index(name)
+        lo, hi = int(self.zone_ptr[name]), int(self.zone_ptr[name + 1])
+        return {k: a[lo:hi] for k, a in self.arrays.items()}
+
+
+def _boundary_result(mesh, out, mask, names):
+    zp, faces, _, _ = mesh.boundary_index()
+    rows = {BOUNDARY_NAMES[k]: out[i] for i, k in enumerate(k for k in range(len(BOUNDARY_NAMES)) if mask >> k & 1)}
+    return BoundaryFields(zp, faces, {name: rows[name] for name in names}, mesh.arrays.get("zone_names"))
+
+
+def boundary_fields(mesh, u, v, w, p, rho, mu, names=BOUNDARY_NAMES, raise_on_error=True):
+    """orc_boundary_fields: the boundary-face maps (BOUNDARY_NAMES or a bit mask) of host fields in ORC cell order ->
+    BoundaryFields (raise_on_error=False: (status, BoundaryFields or None))"""
+    u, v, w, p = map(_f64, (u, v, w, p))
+    for a in (u, v, w, p):
+        assert len(a) == mesh.n_cells
+    mask, names = _mask_of(names, BOUNDARY_NAMES)
+    nb = int(mesh.boundary_index()[0][-1])
+    out = np.zeros((max(bin(mask).count("1"), 1), nb))
+    st = lib().orc_boundary_fields(mesh.ptr, _p(u), _p(v), _p(w), _p(p), C.c_double(rho), C.c_double(mu), C.c_uint32(mask & 0xFFFFFFFF),
+                                   _p(out))
+    if raise_on_error:
+        check(st)
+        return _boundary_result(mesh, out, mask, names)
+    return st, (_boundary_result(mesh, out, mask, names) if st == 0 else None)
+
+
 class Solver:
     """Device-resident state of one solve_steady call (OrcSolver*): what bench.py drives."""
 
@@ -293,6 +385,29 @@ class Solver:
             check(st)
             return rep
         return st, rep
+
+    def derived_fields(self, names_or_mask, raise_on_error=True):
+        """orc_solver_derived_fields: derived cell fields of the current u, v, w (DERIVED_NAMES, 'vorticity' = (n, 3), or a bit
+        mask), cell order as get_fields() -> {name: ndarray} (raise_on_error=False: (status, dict)); reads only"""
+        mask, names = _mask_of(names_or_mask, DERIVED_NAMES, _VORTICITY)
+        out = np.zeros((max(bin(mask).count("1"), 1), self.n))
+        st = lib().orc_solver_derived_fields(self.ptr, C.c_uint32(mask & 0xFFFFFFFF), _p(out))
+        if raise_on_error:
+            check(st)
+            return _derived_dict(out, mask, names, self.n)
+        return st, (_derived_dict(out, mask, names, self.n) if st == 0 else {})
+
+    def boundary_fields(self, names=BOUNDARY_NAMES, raise_on_error=True):
+        """orc_solver_boundary_fields: the boundary-face maps of the current state -> BoundaryFields (raise_on_error=False:
+        (status, BoundaryFields or None)); reads only"""
+        mask, names = _mask_of(names, BOUNDARY_NAMES)
+        nb = int(self.mesh.boundary_index()[0][-1])
+        out = np.zeros((max(bin(mask).count("1"), 1), nb))
+        st = lib().orc_solver_boundary_fields(self.ptr, C.c_uint32(mask & 0xFFFFFFFF), _p(out))
+        if raise_on_error:
+            check(st)
+            return _boundary_result(self.mesh, out, mask, names)
+        return st, (_boundary_result(self.mesh, out, mask, names) if st == 0 else None)
 
     def assemble_momentum(self):
         nnz, n = self.mesh.nnz, self.n
