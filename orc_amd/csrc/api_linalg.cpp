@@ -6,6 +6,23 @@
 namespace orc {
 static SolveStats g_last_stats;
 SolveStats &last_stats() { return g_last_stats; }
+
+// A user matrix on the device: the pattern from CSR, the values uploaded and imported into the SELL image, and the view on both.
+struct UserMatrix {
+    SellMatrix pat;
+    DevBuf<double> csr_vals, vals;
+    MatView view;
+    int load(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, const double *values) {
+        ORC_TRY(sell_from_csr_host(n, n, row_ptr, col_idx, pat));
+        ORC_TRY(csr_vals.upload(values, (size_t)pat.nnz));
+        ORC_TRY(vals.alloc((size_t)std::max<int64_t>(pat.padded, 1)));
+        ORC_TRY(sell_import_values(pat, csr_vals.p, vals.p));
+        view.P = pat.dev();
+        view.val = vals.p;
+        view.symmetric = pat.symmetric;
+        return ORC_OK;
+    }
+};
 }  // namespace orc
 
 extern "C" {
@@ -17,24 +34,17 @@ int orc_iterative_solve(int64_t n, const int64_t *row_ptr, const int64_t *col_id
     ORC_TRY(ensure_init());
     if (n < 0 || !row_ptr || (!col_idx && n > 0) || (!values && n > 0) || !b || !solution_vector)
         return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
-    SellMatrix pat;
-    ORC_TRY(sell_from_csr_host(n, n, row_ptr, col_idx, pat));
+    UserMatrix m;
+    ORC_TRY(m.load(n, row_ptr, col_idx, values));
     const size_t nn = (size_t)std::max<int64_t>(n, 1);
-    DevBuf<double> csr_vals, vals, db, dx;
-    ORC_TRY(csr_vals.upload(values, (size_t)pat.nnz));
-    ORC_TRY(vals.alloc((size_t)std::max<int64_t>(pat.padded, 1)));
-    ORC_TRY(sell_import_values(pat, csr_vals.p, vals.p));
+    DevBuf<double> db, dx;
     ORC_TRY(db.alloc(nn));
     ORC_TRY(dx.alloc(nn));
     ORC_TRY(db.upload(b, (size_t)n));
     ORC_TRY(dx.upload(solution_vector, (size_t)n));
-    MatView A;
-    A.P = pat.dev();
-    A.val = vals.p;
-    A.symmetric = pat.symmetric;
     Arena arena;
     g_last_stats = SolveStats();
-    int st = iterative_solve_dev(A, db.p, dx.p, iteration_count, method, relaxation_factor, convergence_threshold, preconditioner,
+    int st = iterative_solve_dev(m.view, db.p, dx.p, iteration_count, method, relaxation_factor, convergence_threshold, preconditioner,
                                  arena, &g_last_stats);
     // the reference mutates solution_vector in place up to the panic; hand back what was computed
     int st2 = dx.download(solution_vector, (size_t)n);
@@ -160,21 +170,13 @@ int orc_amg_coarsen(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, c
                     int64_t *out_n_coarse, int64_t *out_nnz, int64_t *out_row_ptr, int64_t *out_col, double *out_val, int *rounds) {
     using namespace orc;
     ORC_TRY(ensure_init());
-    SellMatrix pat;
-    ORC_TRY(sell_from_csr_host(n, n, row_ptr, col_idx, pat));
-    DevBuf<double> csr_vals, vals;
-    ORC_TRY(csr_vals.upload(values, (size_t)pat.nnz));
-    ORC_TRY(vals.alloc((size_t)std::max<int64_t>(pat.padded, 1)));
-    ORC_TRY(sell_import_values(pat, csr_vals.p, vals.p));
-    MatView A;
-    A.P = pat.dev();
-    A.val = vals.p;
-    A.symmetric = pat.symmetric;
+    UserMatrix m;
+    ORC_TRY(m.load(n, row_ptr, col_idx, values));
     Arena arena;
     std::vector<int> choice;
     std::vector<int64_t> rp, ci;
     std::vector<double> v;
-    ORC_TRY(amg_debug_coarsen(A, arena, choice, rp, ci, v, rounds));
+    ORC_TRY(amg_debug_coarsen(m.view, arena, choice, rp, ci, v, rounds));
     if (partner) for (int64_t i = 0; i < n; ++i) partner[i] = choice[(size_t)i];
     if (out_n_coarse) *out_n_coarse = (int64_t)rp.size() - 1;
     if (out_nnz) *out_nnz = (int64_t)ci.size();
@@ -191,21 +193,13 @@ int orc_debug_amg_coarse_product(int64_t n, const int64_t *row_ptr, const int64_
     using namespace orc;
     ORC_TRY(ensure_init());
     if (n < 1 || !row_ptr || !col_idx || !values || !x || !y) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
-    SellMatrix pat;
-    ORC_TRY(sell_from_csr_host(n, n, row_ptr, col_idx, pat));
-    DevBuf<double> csr_vals, vals;
-    ORC_TRY(csr_vals.upload(values, (size_t)pat.nnz));
-    ORC_TRY(vals.alloc((size_t)std::max<int64_t>(pat.padded, 1)));
-    ORC_TRY(sell_import_values(pat, csr_vals.p, vals.p));
-    MatView A;
-    A.P = pat.dev();
-    A.val = vals.p;
-    A.symmetric = pat.symmetric;
+    UserMatrix m;
+    ORC_TRY(m.load(n, row_ptr, col_idx, values));
     Arena arena;
     std::vector<int> choice;
     std::vector<int64_t> rp, ci;
     std::vector<double> v;
-    return amg_debug_coarsen(A, arena, choice, rp, ci, v, nullptr, x, y, scaled, has_window_mirror);
+    return amg_debug_coarsen(m.view, arena, choice, rp, ci, v, nullptr, x, y, scaled, has_window_mirror);
 }
 
 int orc_debug_amg_packed_mirror(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, const double *values, int64_t sizes[5], int32_t *row_len,
@@ -213,18 +207,10 @@ int orc_debug_amg_packed_mirror(int64_t n, const int64_t *row_ptr, const int64_t
     using namespace orc;
     ORC_TRY(ensure_init());
     if (n < 1 || !row_ptr || !col_idx || !values || !sizes) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
-    SellMatrix pat;
-    ORC_TRY(sell_from_csr_host(n, n, row_ptr, col_idx, pat));
-    DevBuf<double> csr_vals, vals;
-    ORC_TRY(csr_vals.upload(values, (size_t)pat.nnz));
-    ORC_TRY(vals.alloc((size_t)std::max<int64_t>(pat.padded, 1)));
-    ORC_TRY(sell_import_values(pat, csr_vals.p, vals.p));
-    MatView A;
-    A.P = pat.dev();
-    A.val = vals.p;
-    A.symmetric = pat.symmetric;
+    UserMatrix m;
+    ORC_TRY(m.load(n, row_ptr, col_idx, values));
     Arena arena;
-    return amg_debug_packed(A, arena, sizes, row_len, pk_ptr, pk_col, pk_val, lptr, lidx, wcol, wsize);
+    return amg_debug_packed(m.view, arena, sizes, row_len, pk_ptr, pk_col, pk_val, lptr, lidx, wcol, wsize);
 }
 
 int orc_debug_coloring(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, int32_t *colors, int32_t *n_colors) {

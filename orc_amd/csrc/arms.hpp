@@ -41,7 +41,7 @@ int jacobi_dev(const MatView &A, const double *b, double *x, uint64_t iteration_
                SolveStats *stats, int *status_out);
 // the BiCGSTAB arm (bicgstab.hip, :247-269)
 int bicgstab_dev(const MatView &A, const double *b, double *x, uint64_t iteration_count, Arena &arena);
-// the Multigrid arm (amg.hip, :270-296); smoother: ORC_SOLVER_BICGSTAB (the reference's) or ORC_SOLVER_MULTICOLOR_GS
+// the Multigrid arm (amg_cycle.hip, :270-296); smoother: ORC_SOLVER_BICGSTAB (the reference's) or ORC_SOLVER_MULTICOLOR_GS
 int multigrid_arm_dev(const MatView &A, const double *b, double *x, uint64_t iteration_count, double relaxation_factor,
                       double convergence_threshold, int preconditioner, Arena &arena, SolveStats *stats, int smoother);
 // extension: multicolour Gauss-Seidel and GS-preconditioned BiCGSTAB (gs.hip)
@@ -58,7 +58,7 @@ SolveStats &last_stats();
 // ---- test and bench hooks behind the orc_debug_* / orc_bench_* entries of include/orc_amd.h
 // product launches per kernel family (spmv.hip)
 int debug_product_launches(long long *out, int n_out, bool reset);
-// counters and single set-up steps of the hierarchy (amg.hip)
+// counters and single set-up steps of the hierarchy (amg_pairing.hip, amg_galerkin.hip, amg_mirror.hip, amg_hooks.hip)
 void debug_amg_certification(long long out[2], bool reset);
 void debug_amg_setup_stats(long long out[16], bool reset);
 long long debug_shared_galerkin(bool reset);

@@ -17,7 +17,7 @@ struct Config {
     bool early_p_hierarchy = true;      // ORC_EARLY_P_HIERARCHY: the p' hierarchy is built beside the momentum solves
     int stream_priorities = 3;          // ORC_STREAM_PRIORITIES: 3 solve class above set-up class, 2 the reverse, 1 by lane, 0 none (runtime.cpp)
     bool halo_overlap = true;           // ORC_HALO_OVERLAP: level-0 products of a partitioned mesh run their interior rows beside the exchange
-    // ---- hierarchy set-up (amg.hip)
+    // ---- hierarchy set-up (amg_*.hip)
     bool amg_da = true;                 // ORC_AMG_DA: pairing by deferred acceptance (0: the lock-step rounds only — the fallback)
     int amg_da_steps = 1 << 22;         // ORC_AMG_DA_STEPS: proposals per chain before it is cut (test hook: the fallback finishes the job)
     int amg_da_group = 0;               // ORC_AMG_DA_GROUP: lanes per chain (0: by row length)

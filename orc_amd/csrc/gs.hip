@@ -5,7 +5,7 @@
 // "multicolour GS-preconditioned BiCGSTAB" and an "AMG V-cycle (GS smoother)", so this file provides
 //   ORC_SOLVER_MULTICOLOR_GS        iteration_count sweeps of the reference's row update (:225-239) in colour order,
 //   ORC_SOLVER_BICGSTAB_GS_PRECOND  the reference's BiCGSTAB recurrences, right-preconditioned by one GS sweep,
-//   ORC_SOLVER_MULTIGRID_GS         the Multigrid arm with GS sweeps as its smoother (amg.hip).
+//   ORC_SOLVER_MULTIGRID_GS         the Multigrid arm with GS sweeps as its smoother (amg_cycle.hip).
 // Rows of one colour share no matrix entry, so a colour is one fully parallel kernel and the sweep is a true
 // Gauss-Seidel in colour order; the row sum runs in ascending-column order like everything else.
 // Colouring: speculative first-fit with conflict resolution by a deterministic hash priority (64-bit colour mask), on

@@ -188,12 +188,19 @@ struct AmgHierarchy {
         PackedDev pk;
         XWinDev xw;
         RowsDev rows;
+        bool rows_transient = false;  // set-up only: `rows` lives in the scratch arena's companion, valid until the next level has been built
         int64_t n = 0, padded = 0;
         int rounds = 0;
     } level[4];
     int n_levels = 0;
     int64_t n_fine = 0;
 };
+// A built level's operator as the solves and the next level's set-up see it (halo stays null: coarse levels are solved per rank)
+inline MatView coarse_view(const AmgHierarchy::Level &L, bool symmetric) {
+    MatView V;
+    V.P = L.P; V.val = L.val; V.pk = L.pk; V.xw = L.xw; V.rows = L.rows; V.symmetric = symmetric;
+    return V;
+}
 
 // The u, v and w momentum systems of one SIMPLE iteration share their pattern and differ in a few coefficients (the TVD
 // limiter per component), and their greedy pairings come out the same for all but a handful of rows (measured: 100.00 %
@@ -216,9 +223,9 @@ struct SiblingPairing {
     const int *wait(int level, int64_t rows, hipStream_t stream);                 // follower; null = start from scratch
     void finish();                     // leader, on every exit from its solve
 
-    // [r04] One Galerkin pass for the systems that share the fine pairing (multigrid_prepare_dev; amg.hip: GalerkinSibling).  A follower
+    // [r04] One Galerkin pass for the systems that share the fine pairing (multigrid_prepare_dev in amg_cycle.hip; amg.hpp: GalerkinSibling).  A follower
     // OFFERS its fine view and arenas and blocks; the leader, through with its fine aggregation, COLLECTS the offers, checks its pairing
-    // against every offered matrix (agg_verify_k), builds the first coarse operators of all that agree in one pass and ANSWERS; a follower
+    // against every offered matrix (pairing_mismatches), builds the first coarse operators of all that agree in one pass and ANSWERS; a follower
     // whose answer is "adopted" continues with the second level, any other one falls back to wait() and its own product.  All hand-overs
     // go through mu / cv, so the leader may allocate in a blocked follower's arenas.
     struct Offer {
@@ -227,13 +234,13 @@ struct SiblingPairing {
         Arena *arena = nullptr, *rows_arena = nullptr;
         hipEvent_t view_ready = nullptr;        // recorded on the follower's stream once its view (scalings) is complete
         bool answered = false, adopted = false;
-        void *level = nullptr;                  // CoarseLevel the leader fills (owned by the follower's stack frame)
+        AmgHierarchy::Level *level = nullptr;   // the level the leader fills (owned by the follower's stack frame)
     } offer[2];
     int expected_offers = 0;                    // followers that WILL speak (set before the leader starts: set_expected)
     hipEvent_t ops_ready = nullptr;             // recorded on the leader's stream behind the shared pass
     const int *lead_choice = nullptr, *lead_chooser = nullptr;  // the leader's own arrays (alive as long as its hierarchy)
     void set_expected(int n);
-    int make_offer(int slot, const MatView *view, Arena *arena, Arena *rows_arena, void *level, hipStream_t stream);  // follower
+    int make_offer(int slot, const MatView *view, Arena *arena, Arena *rows_arena, AmgHierarchy::Level *level, hipStream_t stream);  // follower
     void withdraw(int slot);                                                                                          // follower, instead of an offer
     bool wait_answer(int slot, hipStream_t stream);  // follower: true = its level was built by the leader (stream waits for it)
     int collect_offers(Offer *out[2]);               // leader: blocks until every expected follower has spoken; returns how many offered

@@ -1,4 +1,4 @@
-// linalg_kernels.hpp — device-side building blocks shared by the solver translation units (spmv.hip, bicgstab.hip, jacobi.hip, cg.hip, amg.hip, ...).
+// linalg_kernels.hpp — device-side building blocks shared by the solver translation units (spmv.hip, bicgstab.hip, jacobi.hip, cg.hip, amg_*.hip, ...).
 #pragma once
 #include "linalg.hpp"
 

@@ -1,6 +1,6 @@
 """Case table of the AMG set-up tests (tests/test_amg_cases_cpu.py, tests/test_gpu_amg_cases.py) and two plain references.
 
-The Multigrid set-up (orc_amd/csrc/amg.hip: the pairing da_first_k / da_chase_k / agg_verify_k, the Galerkin product galerkin_bound_k /
+The Multigrid set-up (orc_amd/csrc/amg_pairing.hip, amg_galerkin.hip: the pairing da_first_k / da_chase_k / agg_verify_k, the Galerkin product galerkin_bound_k /
 galerkin_merge_k) takes any user CSR matrix and branches on quantities a finite-volume matrix never moves:
   * the LDS tier of a coarse row: its candidate count c (the summed lengths of its <= 4 fine rows) goes to the narrowest tier t = 0..6 with
     64 << t >= 2 c, i.e. tier t holds c <= 32 << t; above c = 2048 the set-up refuses;

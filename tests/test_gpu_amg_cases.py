@@ -60,7 +60,7 @@ def assert_same_csr(x, y, what):
 
 
 def expected_lanes(a):
-    """amg.hip aggregate(): 4 lanes per chain when the SELL-64 image holds at most 24 entries per row on average, else 8"""
+    """amg_pairing.hip aggregate(): 4 lanes per chain when the SELL-64 image holds at most 24 entries per row on average, else 8"""
     n = a.shape[0]
     lens = np.zeros(((n + 63) // 64) * 64, np.int64)
     lens[:n] = np.diff(a.indptr)

@@ -93,7 +93,7 @@ def test_multigrid_arm_three_systems_bit_identical(gpu, shape, distinct, precond
 @pytest.mark.parametrize("shape", [(20, 17, 9), (64, 40, 12)])
 @pytest.mark.parametrize("odd_one", [1, 2])
 def test_shared_galerkin_pass_with_one_sibling_and_switched_off(gpu, monkeypatch, shape, odd_one):
-    """[r04] The shared Galerkin pass (amg.hip: MergeSiblings; linear_algebra.rs:80-84 per system) with TWO value sets: one of v / w has a
+    """[r04] The shared Galerkin pass (amg_galerkin.hip: MergeSiblings; linear_algebra.rs:80-84 per system) with TWO value sets: one of v / w has a
     pairing of its own and multiplies for itself, the other rides with u.  And ORC_AMG_SHARED_GALERKIN=0 (every system for itself, r03)
     gives the same bits."""
     from orc_amd.linear_algebra import iterative_solve, iterative_solve3, shared_galerkin
