@@ -503,6 +503,16 @@ int orc_debug_amg_coarse_product(int64_t n, const int64_t *row_ptr, const int64_
  * are written only if none of them is null, so a caller asks for the sizes first. */
 int orc_debug_amg_packed_mirror(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, const double *values, int64_t sizes[5], int32_t *row_len,
                                 int64_t *pk_ptr, int32_t *pk_col, double *pk_val, int64_t *lptr, uint16_t *lidx, int32_t *wcol, int32_t *wsize);
+/* [r08] orc_debug_amg_xwin_raw: the same set-up, and the level's window streams byte for byte as the products read them (ORC_XWIN_COMPACT; the hook
+ * above keeps returning the wide image, expanded on the host where the level is stored compactly).  info = {coarse rows, slices, 256-row blocks
+ * (0: no mirror), window-position slots, bits per position (12 where the level's LDS share is at most 4096 entries, else 16), bytes of the position
+ * stream, the level's LDS share in entries, blocks with 16-bit window columns, blocks with a window and 32-bit columns, bytes of window columns a
+ * product reads}.  A granule of eight 12-bit positions is 12 bytes, position u in bits [12 u, 12 u + 12) of its 96, slice s at byte 1.5 lptr[s].
+ * A block owns 5000 words of wcol_raw: with wfmt[b] = 0 its wsize[b] columns, with wfmt[b] = 1 ceil(wsize[b] / 64) bases (the column of list entry
+ * 64 s) followed by wsize[b] 16-bit offsets from the base of the entry's segment.  The arrays (lptr [slices + 1], pos_raw [bytes of the position
+ * stream], wcol_raw [blocks * 5000], wsize / wfmt [blocks]) are written only if none of them is null, so a caller asks for info first. */
+int orc_debug_amg_xwin_raw(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, const double *values, int64_t info[10], int64_t *lptr,
+                           unsigned char *pos_raw, int32_t *wcol_raw, int32_t *wsize, int32_t *wfmt);
 /* collectives this process has issued since the last reset — halo exchanges (one grouped ncclSend/ncclRecv launch each) and
  * all-reduces, status agreements included: the latency-bound messages of a partitioned SIMPLE iteration */
 long long orc_debug_collectives(int reset);

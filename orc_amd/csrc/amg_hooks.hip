@@ -1,9 +1,11 @@
 // amg_hooks.hip — test hooks: one level of the set-up (aggregate() + galerkin(), private functions of the reference) made observable.
 //   amg_debug_coarsen   the pairing and the coarse operator in CSR, optionally a product with it as the solves multiply it (orc_amg_coarsen,
 //                       orc_debug_amg_coarse_product)
-//   amg_debug_packed    the level's packed mirror and windows copied to the host (orc_debug_amg_packed_mirror)
+//   amg_debug_packed    the level's packed mirror and windows copied to the host (orc_debug_amg_packed_mirror), compact streams expanded
+//   amg_debug_xwin_raw  the windows' streams byte for byte as the products read them, and what they count (orc_debug_amg_xwin_raw)
 // Both leave the arena as they found it on every exit (ArenaScope).
 #include <algorithm>
+#include <cstring>
 
 #include "amg.hpp"
 
@@ -72,8 +74,30 @@ int amg_debug_coarsen(const MatView &A, Arena &arena, std::vector<int> &choice_h
     return ORC_OK;
 }
 
+// The compact window formats (XWinDev: pos12, wfmt) expanded on the host to the wide ones.  raw: the position stream, n_slots positions;
+// words: one block's kXWinCap words of wcol.
+static void expand_positions12(const unsigned *raw, int64_t n_slots, uint16_t *out) {
+    for (int64_t g = 0; g < n_slots / kPackChunk; ++g) {
+        const unsigned long long lo = raw[3 * g] | (unsigned long long)raw[3 * g + 1] << 32, hi = raw[3 * g + 1] >> 16 | (unsigned long long)raw[3 * g + 2] << 16;
+        for (int u = 0; u < 4; ++u) {
+            out[kPackChunk * g + u] = (uint16_t)(lo >> (12 * u) & 0xfffu);
+            out[kPackChunk * g + 4 + u] = (uint16_t)(hi >> (12 * u) & 0xfffu);
+        }
+    }
+}
+static void expand_window16(int32_t *words, int ws) {
+    const int nseg = (ws + kXWinSeg - 1) / kXWinSeg;
+    const std::vector<int32_t> base(words, words + nseg);
+    std::vector<uint16_t> off((size_t)ws);
+    memcpy(off.data(), words + nseg, sizeof(uint16_t) * (size_t)ws);
+    for (int j = 0; j < ws; ++j) words[j] = base[(size_t)(j / kXWinSeg)] + (int32_t)off[(size_t)j];
+}
+// bytes of a level's position stream
+static size_t position_bytes(const XWinDev &xw, int64_t n_slots) { return (size_t)n_slots * (xw.pos12 ? 3 : 4) / 2; }
+
 // One level of the set-up on A, as amg_debug_coarsen, and the level's packed mirror and windows copied to the host (PackedDev, XWinDev):
 // sizes = {coarse rows, slices, value slots, position slots, blocks}; with any output pointer null only the sizes are written.
+// lidx_h and wcol_h are the WIDE image whatever the level stores: 16-bit positions, 32-bit columns.
 int amg_debug_packed(const MatView &A, Arena &arena, int64_t sizes[5], int32_t *row_len_h, int64_t *pk_ptr_h, int32_t *pk_col_h, double *pk_val_h,
                      int64_t *lptr_h, uint16_t *lidx_h, int32_t *wcol_h, int32_t *wsize_h) {
     hipStream_t st = ctx().stream;
@@ -91,10 +115,54 @@ int amg_debug_packed(const MatView &A, Arena &arena, int64_t sizes[5], int32_t *
         ORC_HIP(hipMemcpyAsync(pk_col_h, L.pk.col, sizeof(int32_t) * (size_t)sizes[2], hipMemcpyDeviceToHost, st));
         ORC_HIP(hipMemcpyAsync(pk_val_h, L.pk.val, sizeof(double) * (size_t)sizes[2], hipMemcpyDeviceToHost, st));
         ORC_HIP(hipMemcpyAsync(lptr_h, L.xw.lptr, sizeof(int64_t) * (size_t)(ns + 1), hipMemcpyDeviceToHost, st));
-        ORC_HIP(hipMemcpyAsync(lidx_h, L.xw.lidx, sizeof(uint16_t) * (size_t)sizes[3], hipMemcpyDeviceToHost, st));
+        std::vector<unsigned> raw(L.xw.pos12 ? position_bytes(L.xw, sizes[3]) / 4 : 0);
+        std::vector<int32_t> wfmt((size_t)nb);
+        if (L.xw.pos12) ORC_HIP(hipMemcpyAsync(raw.data(), L.xw.lidx, position_bytes(L.xw, sizes[3]), hipMemcpyDeviceToHost, st));
+        else ORC_HIP(hipMemcpyAsync(lidx_h, L.xw.lidx, sizeof(uint16_t) * (size_t)sizes[3], hipMemcpyDeviceToHost, st));
         ORC_HIP(hipMemcpyAsync(wcol_h, L.xw.wcol, sizeof(int32_t) * (size_t)(nb * kXWinCap), hipMemcpyDeviceToHost, st));
         ORC_HIP(hipMemcpyAsync(wsize_h, L.xw.wsize, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipMemcpyAsync(wfmt.data(), L.xw.wfmt, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, st));
         ORC_HIP(hipStreamSynchronize(st));
+        if (L.xw.pos12) expand_positions12(raw.data(), sizes[3], lidx_h);
+        for (int64_t b = 0; b < nb; ++b)
+            if (wfmt[(size_t)b] && wsize_h[b] > 0) expand_window16(wcol_h + b * kXWinCap, wsize_h[b]);
+    }
+    return ORC_OK;
+}
+
+// The same level's window streams as they are stored.  info = {coarse rows, slices, blocks, position slots, bits per position (12 / 16; 0: no
+// mirror), bytes of the position stream, the level's LDS share in entries, blocks with 16-bit columns, blocks with a window and 32-bit columns,
+// bytes of window columns a product reads (4 per entry, or 2 per entry and 4 per started segment of 64)}; the arrays (lptr [slices + 1],
+// pos_raw [bytes of the position stream], wcol_raw [blocks * kXWinCap words], wsize / wfmt [blocks]) are written only if none is null.
+int amg_debug_xwin_raw(const MatView &A, Arena &arena, int64_t info[10], int64_t *lptr_h, unsigned char *pos_raw_h, int32_t *wcol_raw_h, int32_t *wsize_h, int32_t *wfmt_h) {
+    hipStream_t st = ctx().stream;
+    ArenaScope scope(arena);
+    AmgHierarchy::Level L;
+    ORC_TRY(build_level(A, arena, L));
+    const bool mirror = L.pk.ptr && L.xw.lidx;
+    const int64_t ns = L.P.n_slices, nb = (ns + 3) / 4;
+    for (int i = 0; i < 10; ++i) info[i] = 0;
+    info[0] = L.n; info[1] = ns;
+    if (!mirror) return ORC_OK;
+    std::vector<int32_t> wsize((size_t)nb), wfmt((size_t)nb);
+    ORC_HIP(hipMemcpyAsync(&info[3], L.xw.lptr + ns, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ORC_HIP(hipMemcpyAsync(wsize.data(), L.xw.wsize, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, st));
+    ORC_HIP(hipMemcpyAsync(wfmt.data(), L.xw.wfmt, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, st));
+    ORC_HIP(hipStreamSynchronize(st));
+    info[2] = nb; info[4] = L.xw.pos12 ? 12 : 16; info[5] = (int64_t)position_bytes(L.xw, info[3]); info[6] = L.xw.cap;
+    for (int64_t b = 0; b < nb; ++b) {
+        const int64_t ws = wsize[(size_t)b];
+        if (ws <= 0) continue;
+        if (wfmt[(size_t)b]) { ++info[7]; info[9] += 2 * ws + 4 * ((ws + kXWinSeg - 1) / kXWinSeg); }
+        else { ++info[8]; info[9] += 4 * ws; }
+    }
+    if (lptr_h && pos_raw_h && wcol_raw_h && wsize_h && wfmt_h) {
+        ORC_HIP(hipMemcpyAsync(lptr_h, L.xw.lptr, sizeof(int64_t) * (size_t)(ns + 1), hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipMemcpyAsync(pos_raw_h, L.xw.lidx, (size_t)info[5], hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipMemcpyAsync(wcol_raw_h, L.xw.wcol, sizeof(int32_t) * (size_t)(nb * kXWinCap), hipMemcpyDeviceToHost, st));
+        ORC_HIP(hipStreamSynchronize(st));
+        std::copy(wsize.begin(), wsize.end(), wsize_h);
+        std::copy(wfmt.begin(), wfmt.end(), wfmt_h);
     }
     return ORC_OK;
 }

@@ -213,6 +213,17 @@ int orc_debug_amg_packed_mirror(int64_t n, const int64_t *row_ptr, const int64_t
     return amg_debug_packed(m.view, arena, sizes, row_len, pk_ptr, pk_col, pk_val, lptr, lidx, wcol, wsize);
 }
 
+int orc_debug_amg_xwin_raw(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, const double *values, int64_t info[10], int64_t *lptr,
+                           unsigned char *pos_raw, int32_t *wcol_raw, int32_t *wsize, int32_t *wfmt) {
+    using namespace orc;
+    ORC_TRY(ensure_init());
+    if (n < 1 || !row_ptr || !col_idx || !values || !info) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
+    UserMatrix m;
+    ORC_TRY(m.load(n, row_ptr, col_idx, values));
+    Arena arena;
+    return amg_debug_xwin_raw(m.view, arena, info, lptr, pos_raw, wcol_raw, wsize, wfmt);
+}
+
 int orc_debug_coloring(int64_t n, const int64_t *row_ptr, const int64_t *col_idx, int32_t *colors, int32_t *n_colors) {
     using namespace orc;
     ORC_TRY(ensure_init());

@@ -68,6 +68,8 @@ int amg_debug_coarsen(const MatView &A, Arena &arena, std::vector<int> &choice_h
                       int scaled = 0, int *mirror_out = nullptr);
 int amg_debug_packed(const MatView &A, Arena &arena, int64_t sizes[5], int32_t *row_len_h, int64_t *pk_ptr_h, int32_t *pk_col_h, double *pk_val_h,
                      int64_t *lptr_h, uint16_t *lidx_h, int32_t *wcol_h, int32_t *wsize_h);
+int amg_debug_xwin_raw(const MatView &A, Arena &arena, int64_t info[10], int64_t *lptr_h, unsigned char *pos_raw_h, int32_t *wcol_raw_h, int32_t *wsize_h,
+                       int32_t *wfmt_h);
 // the colouring cache, the sweeps alone and the colouring of a pattern (gs.hip)
 void gs_forget_pattern(const void *col_ptr);
 int bench_gs_sweep_dev(const MatView &A, const double *b, double *x, int reps, Arena &arena, float *ms_per_sweep, int *n_colors);

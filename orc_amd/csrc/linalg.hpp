@@ -69,14 +69,26 @@ struct PackedDev {
 // global gathers.
 constexpr int kXWinRows = 256;   // rows per block = 4 slices = one workgroup
 constexpr int kXWinCap = 5000;   // window entries per block: 40 KB of LDS, four workgroups per CU (r02: 4080 "for five" — four were resident)
+constexpr int kXWinPos12Max = 4096;  // the largest LDS share (XWinDev::cap) whose positions fit twelve bits
+constexpr int kXWinSeg = 64;         // window entries per 32-bit base of a block's 16-bit column list
 struct XWinDev {
+    // A block owns kXWinCap words of wcol.  wfmt[b] == 0: its window's columns as they are, one word each.  wfmt[b] == 1 [r08]: ceil(wsize / 64) bases
+    // — the column of list entry 64 s — followed by wsize 16-bit offsets from the base of the entry's segment (2 bytes per entry and 4 per started
+    // segment instead of 4 per entry); a block keeps the words only if a segment of its list spans 65 536 columns or more (half of the channel's
+    // level-2 / 3 blocks span more than that as a whole, so a base per block would not do).  Both kinds share a level and a launch.
     const int32_t *wcol = nullptr;   // [n_blocks * kXWinCap]
     const int32_t *wsize = nullptr;  // [n_blocks], -1 = no window for this block
+    const int32_t *wfmt = nullptr;   // [n_blocks]
     // window positions of the packed entries, per chunk of 8 depths: every lane whose row is longer than 8j owns 8 contiguous positions
     // (16 bytes: one load), back to back in lane order; the positions past the row's end are 0 (a valid window entry, dropped by the select):
     //     pos(r, k) = lptr[r >> 6] + 8 sum_{j' < j} count(j') + 8 |{lanes l < (r & 63) : len(l) > 8j}| + (k & 7),  j = k >> 3
-    const uint16_t *lidx = nullptr;  // [lptr[n_slices]]
-    const int64_t *lptr = nullptr;   // [n_slices+1] offsets of the slices' positions, multiples of 64 (128 bytes)
+    // [r08] pos12: the level's LDS share is at most 4 096 entries (every level of the channel), and a position takes 12 bits: the 8 positions of a
+    // granule are 12 contiguous bytes (one 12-byte load), position u in bits [12 u, 12 u + 12) of the granule's 96; a slice starts at byte
+    // 1.5 lptr[s] (32-byte aligned), pos() above counts the same units.  A block whose window is larger than the share gathers from global memory
+    // and never reads its positions: they are stored modulo 4 096.
+    const uint16_t *lidx = nullptr;  // [lptr[n_slices]] (pos12: three quarters of that, in words)
+    const int64_t *lptr = nullptr;   // [n_slices+1] offsets of the slices' positions, multiples of 64 (128 bytes; pos12: 96)
+    int32_t pos12 = 0;
     // [r05] the LDS entries a product of THIS level provides per workgroup (<= kXWinCap): the smallest of a few sizes that leaves <= 1 % of the
     // level's blocks without a window.  The compiled worst case (5 000 entries = 40 KB) held a CU to four workgroups whatever the level needed
     // (the channel's level 2: 2 200 per block); blocks whose window is larger gather from global memory, as blocks without a window always did.

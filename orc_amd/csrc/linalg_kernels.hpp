@@ -28,6 +28,15 @@ __device__ __forceinline__ T ld_stream(const T *p) {
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef int i32x2_t __attribute__((ext_vector_type(2)));
 typedef double f64x2_t __attribute__((ext_vector_type(2)));
+// a granule of eight 12-bit window positions (XWinDev::pos12): three words at a 4-byte-aligned address, one 12-byte load (the vector type
+// itself has size and alignment 16: the alignment is lowered on the pointee, and the pointer is stepped in words)
+typedef unsigned u32x3_t __attribute__((ext_vector_type(3)));
+typedef u32x3_t u32x3_a4_t __attribute__((aligned(4)));
+template <bool NT>
+__device__ __forceinline__ u32x3_t ld_pos12(const unsigned *p) {
+    if (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4_t *>(p));
+    return *reinterpret_cast<const u32x3_a4_t *>(p);
+}
 
 // The lane's slot (in pairs) of pair group `in` of a packed slice whose group starts at pair `off`; idle lanes read a stored
 // neighbour (the group's first pair, or the pair before an empty group: loads stay unconditional, see spmv_k).  Advances off.
@@ -408,7 +417,10 @@ __global__ __launch_bounds__(kBlock) void spmv3_uniform_k(MatView3 A, const doub
 // 24 wavefronts per CU) was no faster than 8 (92-94 VGPRs) — 233.1 / 226.6 against 226.2 / 227.5 us on level 2, 226.4 / 219.7 against 224.9 / 218.6 on
 // level 3 (scripts/archive/gpu_r05_j.sh): like the per-level LDS share itself (16 -> 20 wavefronts per CU: -1 ... -3 %), occupancy is not what held this
 // product at 4.6-4.8 TB/s; the number of load instructions per entry was (scripts/microbench/xwin_layout.hip)
-template <class Epi, bool kScaled = true, bool kNT = false>
+// [r08] With 5 loads per chunk the product runs at the read ceiling (5.86 TB/s of FETCH_SIZE on levels 2 and 3), so only bytes are left to take:
+// kP12 (XWinDev::pos12, the launch's choice per level) reads a chunk's positions as 12 bytes instead of 16, and a block with wfmt = 1 fills its
+// window from 16-bit column offsets (scripts/microbench/xwin_layout.hip: -2.8 % and -2 ... -3.7 % per launch, -5 ... -6 % together).
+template <class Epi, bool kScaled = true, bool kNT = false, bool kP12 = false>
 __global__ __launch_bounds__(kBlock) void spmv_xwin_k(MatView A, const double *__restrict__ x, Epi epi, double *__restrict__ partials,
                                                       const double *__restrict__ skip_flags) {
     __shared__ double lds[8];
@@ -451,6 +463,7 @@ __global__ __launch_bounds__(kBlock) void spmv_xwin_k(MatView A, const double *_
         const int64_t sb = __builtin_amdgcn_readfirstlane((int)(pk_off & 0xffffffff)) | ((int64_t)__builtin_amdgcn_readfirstlane((int)(pk_off >> 32)) << 32);
         const int64_t lb = __builtin_amdgcn_readfirstlane((int)(lp_off & 0xffffffff)) | ((int64_t)__builtin_amdgcn_readfirstlane((int)(lp_off >> 32)) << 32);
         const u32x4_t *s_pos = reinterpret_cast<const u32x4_t *>(A.xw.lidx + lb);  // one per chunk and live lane
+        const unsigned *s_pos12 = reinterpret_cast<const unsigned *>(A.xw.lidx) + (lb >> 3) * 3;  // kP12: three words per chunk and live lane
         const f64x2_t *s_val = reinterpret_cast<const f64x2_t *>(A.pk.val + sb);   // one per pair and live lane
         int poff = 0, voff = 0;  // wave-uniform running offsets inside the slice, in chunks of positions / pairs of values
         // [r06] One chunk of kC = 8 entries is one 16-byte position load and four 16-byte value loads per lane (PackedDev, XWinDev: lane-major
@@ -462,13 +475,42 @@ __global__ __launch_bounds__(kBlock) void spmv_xwin_k(MatView A, const double *_
             {
                 const unsigned long long m = __ballot(k0 < len);
                 const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                cc = ld_stream<kNT>(s_pos + poff + (k0 < len ? rank : 0));  // (a chunk below the slice width has a live lane: its first slot exists)
+                const int slot = poff + (k0 < len ? rank : 0);  // (a chunk below the slice width has a live lane: its first slot exists)
+                if (kP12) {
+                    const u32x3_t w = ld_pos12<kNT>(s_pos12 + 3 * slot);
+                    cc = u32x4_t{w.x, w.y, w.z, 0u};
+                } else {
+                    cc = ld_stream<kNT>(s_pos + slot);
+                }
                 poff += __popcll(m);
             }
 #pragma unroll
             for (int q = 0; q < kC / 2; ++q) vv[q] = ld_stream<kNT>(s_val + packed_pair(k0 + 2 * q < len, voff));
         };
-        if (ws > 0) {
+        if (ws > 0 && A.xw.wfmt[b]) {  // (workgroup-uniform)
+            // 16-bit column offsets behind the bases of their segments of 64: a wavefront's 64 entries of a pass share one base (a scalar load;
+            // the lanes past the list's end take its last entry, which lies in the last segment); the three phases as below
+            const int nseg = (ws + kXWinSeg - 1) / kXWinSeg;
+            const int32_t *wb = A.xw.wcol + b * kXWinCap;
+            const uint16_t *w16 = reinterpret_cast<const uint16_t *>(wb + nseg);
+            for (int j0 = 0; j0 < ws; j0 += 8 * kBlock) {
+                int wj[8];
+                double xw[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int j = j0 + q * kBlock + (int)threadIdx.x;
+                    const int seg = min((j0 + q * kBlock + wave * 64) / kXWinSeg, nseg - 1);
+                    wj[q] = wb[seg] + (int)ld_stream<kNT>(w16 + (j < ws ? j : ws - 1));
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) xw[q] = x[wj[q]];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int j = j0 + q * kBlock + (int)threadIdx.x;
+                    if (j < ws) xs[j] = xw[q];
+                }
+            }
+        } else if (ws > 0) {
             // window -> LDS: all column loads of a pass are issued before the x gathers, those before the LDS writes
             // (a rolled loop would cost two dependent round trips per element)
             const int32_t *wc = A.xw.wcol + b * kXWinCap;
@@ -503,11 +545,20 @@ __global__ __launch_bounds__(kBlock) void spmv_xwin_k(MatView A, const double *_
                 // waits for the OLDER chunk only (vmcnt retires in order), the younger one travels while it is multiplied.
                 auto consume = [&](int k0, const u32x4_t &cc, const f64x2_t (&vv)[kC / 2]) {
                     double xv[kC];
+                    if (kP12) {
+                        // position u sits in bits [12 u, 12 u + 12) of the granule: its LDS byte offset (x 8) is a shift and a mask, with one
+                        // alignbit for each of the two positions that straddle a word
+                        const unsigned w0 = cc[0], w1 = cc[1], w2 = cc[2];
+                        const unsigned o[kC] = {w0 << 3, w0 >> 9, __builtin_amdgcn_alignbit(w1, w0, 21), w1 >> 1, w1 >> 13, __builtin_amdgcn_alignbit(w2, w1, 25), w2 >> 5, w2 >> 17};
 #pragma unroll
-                    for (int q = 0; q < kC / 2; ++q) {
-                        const unsigned w = cc[q];
-                        xv[2 * q] = xs[w & 0xffffu];
-                        xv[2 * q + 1] = xs[w >> 16];
+                        for (int u = 0; u < kC; ++u) xv[u] = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(xs) + (o[u] & 0x7ff8u));
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < kC / 2; ++q) {
+                            const unsigned w = cc[q];
+                            xv[2 * q] = xs[w & 0xffffu];
+                            xv[2 * q + 1] = xs[w >> 16];
+                        }
                     }
 #pragma unroll
                     for (int u = 0; u < kC; ++u) {

@@ -204,6 +204,15 @@ static void launch_uniform(const MatView &A, int g, const double *x, const Epi &
     else launch_uniform_as<Epi, kMesh, kNarrow, false, false>(A, g, ctx().stream, x, epi, partials, skip_flags);
 }
 
+// One launch of the window product by its template arguments: scaled view or materialised values, cache policy (MatView::nt), and the level's
+// position format (XWinDev::pos12)
+template <class Epi, bool kP12>
+static void launch_xwin(const MatView &A, int g, size_t smem, bool scaled, const double *x, const Epi &epi, double *partials, const double *skip_flags) {
+    if (!scaled && A.nt) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_xwin_k<Epi, false, true, kP12>), dim3(g), dim3(kBlock), smem, ctx().stream, A, x, epi, partials, skip_flags);
+    else if (!scaled) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_xwin_k<Epi, false, false, kP12>), dim3(g), dim3(kBlock), smem, ctx().stream, A, x, epi, partials, skip_flags);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_xwin_k<Epi, true, false, kP12>), dim3(g), dim3(kBlock), smem, ctx().stream, A, x, epi, partials, skip_flags);
+}
+
 // Every product of one system: sizes the grid, refreshes the ghost entries of x (or overlaps that with the interior rows) and picks the
 // kernel by the view.  *grid_out: the partial sums written per reduction.
 template <class Epi>
@@ -225,9 +234,8 @@ static int launch_spmv(const MatView &A_in, const double *x, const Epi &epi, dou
     if (A.halo) ORC_TRY(A.halo->exchange(const_cast<double *>(x)));  // C1: refresh the ghost entries of x
     if (xwin) {
         const size_t xwin_smem = sizeof(double) * (size_t)std::max(1, std::min(A.xw.cap, kXWinCap));
-        if (!scaled && A.nt) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_xwin_k<Epi, false, true>), dim3(g), dim3(kBlock), xwin_smem, ctx().stream, A, x, epi, partials, skip_flags);
-        else if (!scaled) hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_xwin_k<Epi, false>), dim3(g), dim3(kBlock), xwin_smem, ctx().stream, A, x, epi, partials, skip_flags);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_xwin_k<Epi>), dim3(g), dim3(kBlock), xwin_smem, ctx().stream, A, x, epi, partials, skip_flags);
+        if (A.xw.pos12) launch_xwin<Epi, true>(A, g, xwin_smem, scaled, x, epi, partials, skip_flags);
+        else launch_xwin<Epi, false>(A, g, xwin_smem, scaled, x, epi, partials, skip_flags);
         count_launch(kFamWindow);
     } else if (A.pk.ptr) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_k<Epi, kSpmvPacked>), dim3(g), dim3(kBlock), 0, ctx().stream, A, x, epi, partials, skip_flags);

@@ -180,6 +180,61 @@ def amg_packed_mirror(a):
     return out
 
 
+def xwin_unpack_positions(raw, bits):
+    """The window positions of a raw position stream (amg_xwin_raw) as uint16: 16-bit positions as they are; 12-bit ones from granules
+    of 12 bytes that hold eight positions, position u in bits [12 u, 12 u + 12) of the granule's 96 (little-endian)."""
+    raw = np.ascontiguousarray(raw, np.uint8)
+    if bits == 16:
+        return raw.view(np.uint16).copy()
+    assert bits == 12 and len(raw) % 12 == 0
+    w = raw.view(np.uint32).reshape(-1, 3).astype(np.uint64)
+    lo = w[:, 0] | (w[:, 1] << np.uint64(32))            # bits 0..63
+    hi = (w[:, 1] >> np.uint64(16)) | (w[:, 2] << np.uint64(16))  # bits 48..95
+    out = np.empty((len(w), 8), np.uint16)
+    for u in range(4):
+        out[:, u] = (lo >> np.uint64(12 * u)) & np.uint64(0xfff)
+        out[:, 4 + u] = (hi >> np.uint64(12 * u)) & np.uint64(0xfff)
+    return out.reshape(-1)
+
+
+def xwin_unpack_window(words, wsize, fmt):
+    """The wsize ascending columns of one block's window from its words of the raw column stream (amg_xwin_raw): fmt 0 — the columns
+    themselves; fmt 1 — ceil(wsize / 64) bases, then wsize 16-bit offsets from the base of the entry's segment of 64."""
+    words = np.ascontiguousarray(words, np.int32)
+    if wsize <= 0:
+        return np.empty(0, np.int32)
+    if not fmt:
+        return words[:wsize].copy()
+    nseg = (wsize + 63) // 64
+    off = words[nseg:nseg + (wsize + 1) // 2].view(np.uint16)[:wsize].astype(np.int32)
+    return words[:nseg][np.arange(wsize) // 64] + off
+
+
+def amg_xwin_raw(a):
+    """Test hook: the window streams of the coarse level of a (as amg_coarsen builds it) byte for byte as its products read them.
+    Returns None when the level has no mirror, else a dict: pos_bits (12 / 16), pos_bytes, cap (the level's LDS share), blocks_col16 /
+    blocks_col32 (blocks with a window by column format), wcol_bytes (what a product reads of the column lists), pos_slots, lptr,
+    pos_raw (uint8), wcol_raw ([blocks, 5000] int32 words), wsize, wfmt."""
+    a = a.tocsr()
+    a.sort_indices()
+    n = a.shape[0]
+    rp, ci, v = _i64(a.indptr), _i64(a.indices), _f64(a.data)
+    info = np.zeros(10, np.int64)
+    f = lib().orc_debug_amg_xwin_raw
+    head = (C.c_int64(n), _p(rp, C.c_int64), _p(ci, C.c_int64), _p(v, C.c_double), _p(info, C.c_int64))
+    check(f(*head, None, None, None, None, None))
+    nc, ns, nb, pos_slots, bits, pos_bytes = (int(t) for t in info[:6])
+    if nb == 0:
+        return None
+    out = dict(lptr=np.empty(ns + 1, np.int64), pos_raw=np.empty(pos_bytes, np.uint8), wcol_raw=np.empty((nb, 5000), np.int32),
+               wsize=np.empty(nb, np.int32), wfmt=np.empty(nb, np.int32))
+    check(f(*head, _p(out["lptr"], C.c_int64), _p(out["pos_raw"], C.c_uint8), _p(out["wcol_raw"], C.c_int32), _p(out["wsize"], C.c_int32),
+            _p(out["wfmt"], C.c_int32)))
+    out.update(pos_bits=int(info[4]), pos_bytes=int(info[5]), cap=int(info[6]), blocks_col16=int(info[7]), blocks_col32=int(info[8]),
+               wcol_bytes=int(info[9]), pos_slots=pos_slots)
+    return out
+
+
 def xwin_counters(reset=False):
     """Test hook: (blocks described, blocks without a window because of the cap, ... because of the column span) since the last reset"""
     out = (C.c_longlong * 3)()

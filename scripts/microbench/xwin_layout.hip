@@ -6,6 +6,9 @@
 // A synthetic coarse level: `rows` rows of uniformly random length in [lo, hi], one workgroup per block of 256 rows, a window of
 // `ws` sorted columns per block staged in LDS, positions random in the window.  Both kernels add every row in ascending k with the
 // same select, so y must agree bit for bit.  --global: no window, 32-bit columns and global x gathers (the level-1 question).
+// [r08] Two narrower forms of the chunked layout's metadata, each alone and both together, against the chunked layout (LDS window only):
+//   pos12:  a chunk's 8 positions in 12 bits each — 12 contiguous bytes per live lane, one 12-byte load (needs window <= 4096);
+//   col16:  the window's column list as 16-bit offsets from a 32-bit base per 64 list entries (bases first, then the offsets).
 // Build: hipcc --offload-arch=gfx950 -O3 xwin_layout.hip -o xwin_layout
 //   ./xwin_layout [rows lo hi ws reps [--global]]      (defaults: the channel's level 2 shape, 2 560 000 rows, 25-55 entries, 2 560)
 #include <hip/hip_runtime.h>
@@ -28,17 +31,44 @@ struct Mat {
     const double *val;
     const int *wcol, *wsize;
     int cap;
+    const unsigned *lidx12;          // pos12: 3 words per (chunk, live lane); a slice starts at word pptr * 3 / 8
+    const int *wcol16;               // col16: per block (stride cap / 2 + 128 words) ceil(ws / 64) bases, then ws 16-bit offsets
 };
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
+// three words loaded at once from a 4-byte-aligned address (the vector type itself has size and alignment 16)
+typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
+typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
 
 template <class T>
 __device__ __forceinline__ T ldnt(const T *p) { return __builtin_nontemporal_load(p); }
 
+template <bool kCol16 = false>
 __device__ __forceinline__ void load_window(const Mat &A, int64_t b, const double *__restrict__ x, double *xs) {
     const int ws = A.wsize[b];
+    if (kCol16) {
+        const int nseg = (ws + 63) >> 6;
+        const int *wb = A.wcol16 + b * (A.cap / 2 + 128);
+        const unsigned short *w16 = reinterpret_cast<const unsigned short *>(wb + nseg);
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        for (int j0 = 0; j0 < ws; j0 += 8 * 256) {
+            int wj[8];
+            double xw[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {  // the base index j >> 6 is wave-uniform (lanes past the end take the last entry: the same segment)
+                const int j = j0 + q * 256 + (int)threadIdx.x;
+                const int seg = min((j0 + q * 256 + wave * 64) >> 6, nseg - 1);
+                wj[q] = wb[seg] + (int)ldnt(w16 + (j < ws ? j : ws - 1));
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) xw[q] = x[wj[q]];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) { const int j = j0 + q * 256 + (int)threadIdx.x; if (j < ws) xs[j] = xw[q]; }
+        }
+        return;
+    }
     const int *wc = A.wcol + b * A.cap;
     for (int j0 = 0; j0 < ws; j0 += 8 * 256) {
         int wj[8];
@@ -111,17 +141,18 @@ __global__ __launch_bounds__(256) void depth_major_k(Mat A, const double *__rest
 // chunked lane-major layout: 1 + 4 sixteen-byte loads per chunk of 8 entries (--global: 4 x 8-byte column loads instead of the positions)
 struct Chunk {
     u32x4 p;         // 8 positions
+    u32x3 p12;       // pos12: the same in 12 bits each
     i32x2 cg[4];      // --global: columns of pair q
     f64x2 v[4];    // values of pair q
 };
 
-template <bool kGlobal>
+template <bool kGlobal, bool kPos12 = false, bool kCol16 = false>
 __global__ __launch_bounds__(256) void chunked_k(Mat A, const double *__restrict__ x, double *__restrict__ y) {
     extern __shared__ __align__(16) double xs[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t n_blocks = (A.n_slices + 3) >> 2;
     for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
-        if (!kGlobal) load_window(A, b, x, xs);
+        if (!kGlobal) load_window<kCol16>(A, b, x, xs);
         __syncthreads();
         const int64_t slice = b * 4 + wave;
         if (slice < A.n_slices) {
@@ -132,6 +163,7 @@ __global__ __launch_bounds__(256) void chunked_k(Mat A, const double *__restrict
             const int64_t psb = __builtin_amdgcn_readfirstlane((int)(po & 0xffffffff)) | ((int64_t)__builtin_amdgcn_readfirstlane((int)(po >> 32)) << 32);
             const int64_t vsb = __builtin_amdgcn_readfirstlane((int)(vo & 0xffffffff)) | ((int64_t)__builtin_amdgcn_readfirstlane((int)(vo >> 32)) << 32);
             const u32x4 *s_pos = reinterpret_cast<const u32x4 *>(A.lidx + psb);   // one u32x4 per (chunk, live lane)
+            const unsigned *s_pos12 = A.lidx12 + (psb >> 3) * 3;                  // pos12: three words per (chunk, live lane)
             const f64x2 *s_val = reinterpret_cast<const f64x2 *>(A.val + vsb);  // one f64x2 per (chunk, pair, live lane)
             const i32x2 *s_col = reinterpret_cast<const i32x2 *>(A.col + vsb);
             int poff = 0, voff = 0;  // wave-uniform running offsets in 16-byte (positions / value pairs) units
@@ -142,7 +174,9 @@ __global__ __launch_bounds__(256) void chunked_k(Mat A, const double *__restrict
                     const bool in = k0 < len;
                     const unsigned long long m = __ballot(in);
                     const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                    ch.p = ldnt(s_pos + poff + (in ? rank : 0));  // (a chunk below the slice width has a live lane: slot 0 exists)
+                    // (a chunk below the slice width has a live lane: slot 0 exists)
+                    if (kPos12) ch.p12 = __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4 *>(s_pos12 + 3 * (poff + (in ? rank : 0))));
+                    else ch.p = ldnt(s_pos + poff + (in ? rank : 0));
                     poff += __popcll(m);
                 }
 #pragma unroll
@@ -161,6 +195,12 @@ __global__ __launch_bounds__(256) void chunked_k(Mat A, const double *__restrict
                 if (kGlobal) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) { xv[2 * q] = x[ch.cg[q].x]; xv[2 * q + 1] = x[ch.cg[q].y]; }
+                } else if (kPos12) {
+                    // byte offsets into xs (position * 8): a shift and a mask each, an alignbit for the two positions that straddle a word
+                    const unsigned w0 = ch.p12.x, w1 = ch.p12.y, w2 = ch.p12.z;
+                    const unsigned o[8] = {w0 << 3, w0 >> 9, __builtin_amdgcn_alignbit(w1, w0, 21), w1 >> 1, w1 >> 13, __builtin_amdgcn_alignbit(w2, w1, 25), w2 >> 5, w2 >> 17};
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) xv[u] = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(xs) + (o[u] & 0x7ff8u));
                 } else {
                     const unsigned w[4] = {ch.p.x, ch.p.y, ch.p.z, ch.p.w};
 #pragma unroll
@@ -352,5 +392,70 @@ int main(int argc, char **argv) {
                alg / med[w] / 8e6);
     }
     printf("chunked / depth-major: %.3f\n", med[1] / med[0]);
-    return diff != 0;
+    if (global || ws > 4096) return diff != 0;
+
+    // [r08] narrower metadata on the chunked layout: 12-bit positions (3 words per granule of 8) and 16-bit window columns (a base per 64 entries)
+    std::vector<unsigned> lidx12((size_t)pe_new / 8 * 3 + 1, 0u);
+    for (int64_t g = 0; g < pe_new / 8; ++g) {
+        unsigned long long lo48 = 0, hi48 = 0;
+        for (int u = 0; u < 4; ++u) { lo48 |= (unsigned long long)lidx_n[8 * g + u] << (12 * u); hi48 |= (unsigned long long)lidx_n[8 * g + 4 + u] << (12 * u); }
+        lidx12[3 * g] = (unsigned)lo48;
+        lidx12[3 * g + 1] = (unsigned)(lo48 >> 32) | (unsigned)(hi48 << 16);
+        lidx12[3 * g + 2] = (unsigned)(hi48 >> 16);
+    }
+    const int stride16 = ws / 2 + 128, nseg = (ws + 63) / 64;  // words per block
+    std::vector<int> wcol16((size_t)n_blocks * stride16, 0);
+    int64_t wide_segments = 0;
+    for (int64_t b = 0; b < n_blocks; ++b) {
+        int *wb = wcol16.data() + b * stride16;
+        unsigned short *w16 = reinterpret_cast<unsigned short *>(wb + nseg);
+        for (int j = 0; j < ws; ++j) {
+            if ((j & 63) == 0) wb[j >> 6] = wcol[b * ws + j];
+            const int d = wcol[b * ws + j] - wb[j >> 6];
+            wide_segments += d > 65535;
+            w16[j] = (unsigned short)d;
+        }
+    }
+    if (wide_segments) { printf("col16: %lld entries do not fit 16 bits\n", (long long)wide_segments); return 1; }
+    unsigned *d_l12;
+    int *d_w16;
+    double *d_yv;
+    CK(hipMalloc(&d_l12, lidx12.size() * 4)); CK(hipMalloc(&d_w16, wcol16.size() * 4)); CK(hipMalloc(&d_yv, n * 8));
+    CK(hipMemcpy(d_l12, lidx12.data(), lidx12.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_w16, wcol16.data(), wcol16.size() * 4, hipMemcpyHostToDevice));
+    An.lidx12 = d_l12; An.wcol16 = d_w16;
+    auto launch_v = [&](int which, double *y) {
+        if (which == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(chunked_k<false, false, false>), dim3(grid), dim3(256), smem, 0, An, d_x, y);
+        else if (which == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(chunked_k<false, true, false>), dim3(grid), dim3(256), smem, 0, An, d_x, y);
+        else if (which == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(chunked_k<false, false, true>), dim3(grid), dim3(256), smem, 0, An, d_x, y);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(chunked_k<false, true, true>), dim3(grid), dim3(256), smem, 0, An, d_x, y);
+    };
+    const char *vnames[4] = {"chunked", "pos12", "col16", "pos12+col16"};
+    int64_t vdiff[4] = {0, 0, 0, 0};
+    std::vector<double> yv(n);
+    for (int w = 1; w < 4; ++w) {
+        CK(hipMemset(d_yv, 0xff, n * 8));
+        launch_v(w, d_yv);
+        CK(hipGetLastError());
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(yv.data(), d_yv, n * 8, hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < n; ++r) vdiff[w] += memcmp(&yv[r], &y1[r], 8) != 0;
+    }
+    std::vector<float> tv[4];
+    for (int i = 0; i < reps; ++i)
+        for (int w = 0; w < 4; ++w) {
+            CK(hipEventRecord(e0, 0)); launch_v(w, d_yv); CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1)); tv[w].push_back(ms * 1e3f);
+        }
+    const double pos_wide = (double)pe_new * 2, pos_12 = (double)pe_new * 1.5, col_wide = (double)n_blocks * ws * 4, col_16 = (double)n_blocks * (ws * 2 + nseg * 4);
+    printf("metadata bytes: positions %.1f -> %.1f MB, window columns %.1f -> %.1f MB (of %.1f MB streamed per launch)\n", pos_wide / 1e6, pos_12 / 1e6, col_wide / 1e6, col_16 / 1e6,
+           (bytes_n + col_wide + (double)n_blocks * ws * 8) / 1e6);
+    double vmed[4];
+    for (int w = 0; w < 4; ++w) {
+        std::sort(tv[w].begin(), tv[w].end());
+        vmed[w] = tv[w][tv[w].size() / 2];
+        printf("%-12s median %8.1f us  min %8.1f us  max %8.1f us  vs chunked %.3f  bit-identical to chunked: %s\n", vnames[w], vmed[w], (double)tv[w][0], (double)tv[w].back(), vmed[w] / vmed[0],
+               vdiff[w] == 0 ? "yes" : "NO");
+    }
+    return diff != 0 || vdiff[1] != 0 || vdiff[2] != 0 || vdiff[3] != 0;
 }

@@ -4,6 +4,8 @@ then exactly the launches bench.py times — the level-0 products as the BiCGSTA
 systems per launch: orc_bench_inloop_products), the plain product, and one product per level of a_u's Multigrid hierarchy
 (orc_bench_amg_levels: levels 0-1 spmv_uniform_k, levels 2-3 spmv_xwin_k) — `--reps` launches each after one warm launch.
 Run under `rocprofv3 --kernel-trace --stats` and, separately, one `--pmc` pass per counter group (scripts/gpu_pmc.sh).
+With ORC_DEBUG_XWIN=1 in the environment the set-up of that hierarchy prints, per level with windows, the formats it stored (bits per window
+position, blocks and window entries that qualify for 16-bit columns: ORC_XWIN_COMPACT) — the shares profiles/r08_pmc_xwin_products.csv goes with.
 `--workload config5`: the same for BASELINE configs[4]'s per-GPU slab (252 x 100 x 72 blocks of the mixed tet / hex / poly channel, 5.14 M cells)."""
 import argparse
 import os
