@@ -518,6 +518,13 @@ int orc_debug_amg_xwin_raw(int64_t n, const int64_t *row_ptr, const int64_t *col
 long long orc_debug_collectives(int reset);
 int orc_debug_clamp_partials_grid(long long requested);
 int orc_debug_max_partials(void);
+/* Test hook, host only (no device, no orc_init): the schedule a SIMPLE iteration would run for these inputs — the one decision of
+ * orc_amd/csrc/schedule.hpp, which no test of results can see because every schedule computes the same bits.  switches: bit 0
+ * ORC_CONCURRENT_MOMENTUM, 1 ORC_TRIPLE_MOMENTUM, 2 ORC_EARLY_P_HIERARCHY, 3 ORC_TWO_STREAM_MULTIGRID, 4 ORC_AMG_SIBLING (the solver's five
+ * switches), 5 partitioned mesh, 6 ORC_DEBUG_NAN, 7 profiling enabled, 8 the slot-space Gauss-Seidel sweep enabled; the solver types are
+ * OrcSolverType of the momentum systems and of the pressure correction.  Returns momentum + 256 * p_hierarchy with momentum 0 sequential,
+ * 1 lanes, 2 lanes on a partitioned mesh, 3 lock-step and p_hierarchy 0 inside the solve (or none), 1 early, 2 late. */
+int orc_debug_schedule(unsigned switches, int momentum_solver, int p_solver, int reduction_order);
 int orc_debug_amg_certification(long long out[2], int reset);
 /* Test hook: what the calling process's most recent pairing (build_restriction_matrix, linear_algebra.rs:30-60) and the Galerkin product
  * behind it did; not cumulative.  out[0..4] = the deferred-acceptance chains: rows left to them, their proposals, proposals found by a scan of

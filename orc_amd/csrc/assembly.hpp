@@ -203,8 +203,36 @@ int mesh_upload(OrcMesh &m, int64_t n_own, int64_t n_cells, int64_t n_faces, int
                 const double *cell_centroid, const double *cell_volume, const int64_t *cell_face_ptr, const int64_t *cell_faces,
                 const int32_t *zone_type, const double *zone_scalar, const double *zone_vector);
 
+// solver_state.cpp
 int solver_init(SolverState &s, OrcMesh *m, const OrcSettings *settings, double rho, double mu);
-// kernels (all asynchronous on the library stream)
+int fetch_status(SolverState &s);
+
+inline bool is_tvd(int momentum) { return momentum >= ORC_MOMENTUM_TVD_LUD && momentum <= ORC_MOMENTUM_TVD_CD1; }
+
+// a matrix on the mesh pattern (a_u, a_v, a_w, a_p, a_di, the scalar arm's) as the solves see it
+inline MatView mesh_view(const SolverState &s, const double *values) {
+    MatView A;
+    A.P = s.mesh->pat.dev();
+    A.val = values;
+    A.symmetric = s.mesh->pat.symmetric;
+    A.halo = s.mesh->halo.active() ? &s.mesh->halo : nullptr;
+    A.persistent_pattern = true;
+    return A;
+}
+
+// partitioned mesh: the ghost entries of u, v, w, p, and of a gradient [3][n], before a face kernel reads them (C1)
+inline int exchange_fields(SolverState &s) {
+    if (!s.mesh->halo.active()) return ORC_OK;
+    double *f[4] = {s.u.p, s.v.p, s.w.p, s.p.p};
+    return s.mesh->halo.exchange(f, 4);
+}
+inline int exchange_gradient(SolverState &s, double *gp) {
+    if (!s.mesh->halo.active()) return ORC_OK;
+    double *g3[3] = {gp, gp + s.n, gp + 2 * s.n};
+    return s.mesh->halo.exchange(g3, 3);
+}
+
+// assembly.hip: the kernels' launch wrappers (all asynchronous on the calling thread's stream, ctx().stream)
 int k_diffusion(SolverState &s);                 // K14  discretization.rs:39-131
 int k_init_momentum(SolverState &s);             // discretization.rs:450-472
 int k_gradients(SolverState &s, bool need_gu);   // K9   solver.rs:774-802, 874-902
@@ -212,9 +240,11 @@ int k_face_flux(SolverState &s, bool with_pf);   // K10  solver.rs:1007-1150
 int k_momentum(SolverState &s, double *peclet_host /*3, may be null*/);  // K11  discretization.rs:134-356
 int k_time_term(SolverState &s);                 // implicit time term on the momentum systems (transient arm, k_momentum)
 int k_pressure_correction(SolverState &s);       // K12  discretization.rs:359-448
+int k_pressure_matrix(SolverState &s);           // the p' matrix alone from the fresh momentum diagonals: face_coef_k, then pressure_k
 int k_apply_correction(SolverState &s, double *sums_host /*5: p'^2, |dU|^2, sum u, sum v, sum w*/);  // K13 solver.rs:1170-1227
+// simple_iteration.cpp
 int solver_iterate(SolverState &s, uint64_t iterations, double *report);
-int fetch_status(SolverState &s);
+// initialize.hip
 int check_boundary_conditions(const OrcMesh &m);       // solver.rs:710-772: 0 PressureOnly, 1 VelocityOnly, 2 Hybrid, < 0 = -status
 int initialize_pressure_field_dev(SolverState &s);     // solver.rs:414-509
 int initialize_flow_dev(SolverState &s, uint64_t iteration_count);  // solver.rs:246-352

@@ -10,7 +10,7 @@
 namespace orc {
 
 struct Config {
-    // ---- schedule of a SIMPLE iteration (assembly.hip)
+    // ---- schedule of a SIMPLE iteration (simple_iteration.cpp, schedule.hpp)
     bool triple_momentum = true;        // ORC_TRIPLE_MOMENTUM: u, v, w in lock-step on their shared pattern (0: one system per solve)
     bool concurrent_momentum = true;    // ORC_CONCURRENT_MOMENTUM: momentum set-ups / solves on streams and threads of their own
     bool two_stream_multigrid = true;   // ORC_TWO_STREAM_MULTIGRID: the set-up of level l+1 beside the smoothing of level l (one-system arm)

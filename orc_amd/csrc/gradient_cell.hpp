@@ -1,10 +1,13 @@
 // gradient_cell.hpp — the per-cell velocity-gradient arithmetic of the assembly (K9), shared by grad_u_k / grad_u_lsq_k
-// (assembly.hip) and derived_cell_k (derived.hip): the small vector type, the boundary-value rules and the two per-cell bodies.
+// (assembly.hip) and derived_cell_k (derived.hip): the small vector type, the boundary-value rules and the two per-cell bodies;
+// the grid-stride loop of the assembly kernels (assembly.hip, initialize.hip).
 // Device code only.  Every operation and its order are the reference's; a kernel that calls a body gets the same bits as any other.
 #pragma once
 #include "assembly.hpp"
 
 #ifdef __HIPCC__
+#define GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
+
 namespace orc {
 
 struct V3 {

@@ -1,7 +1,7 @@
 // mesh_io.cpp — host side of SURVEY §8(f): io::read_mesh (io.rs:32-515) into a flat host image of mesh::Mesh,
 // the zone lookup of Mesh::get_face_zone (mesh.rs:189-195), and the text checkpoint formats read_data / write_data /
 // write_data_with_precision / write_gradients (io.rs:519-662).  No device work here: orc_mesh_upload hands the arrays
-// to mesh_upload (assembly.hip).  Compiled with -ffp-contract=off like the kernels, so the geometry (io.rs:289-438)
+// to mesh_upload (solver_state.cpp).  Compiled with -ffp-contract=off like the kernels, so the geometry (io.rs:289-438)
 // rounds exactly as the reference's operator chains do.
 #include <cerrno>
 #include <cmath>

@@ -5,6 +5,7 @@
 
 #include "config.hpp"
 #include "linalg.hpp"
+#include "schedule.hpp"
 
 namespace orc {
 
@@ -348,6 +349,15 @@ int64_t orc_breakdown_guard_events(int reset) {
 long long orc_debug_halo_overlaps(void) { return orc::ctx().halo_overlaps; }
 int orc_debug_clamp_partials_grid(long long requested) { return orc::clamp_partials_grid(requested); }
 int orc_debug_max_partials(void) { return orc::kMaxPartials; }
+int orc_debug_schedule(unsigned switches, int momentum_solver, int p_solver, int reduction_order) {
+    orc::ScheduleInputs in;
+    in.concurrent_momentum = switches & 1u; in.triple_momentum = switches & 2u; in.early_p_hierarchy = switches & 4u;
+    in.two_stream_multigrid = switches & 8u; in.sibling_pairing = switches & 16u; in.partitioned = switches & 32u;
+    in.debug_nan = switches & 64u; in.profiling = switches & 128u; in.gs_slot_space = switches & 256u;
+    in.momentum_solver = momentum_solver; in.p_solver = p_solver; in.reduction_order = reduction_order;
+    const orc::Schedule plan = orc::decide_schedule(in);
+    return (int)plan.momentum + 256 * (int)plan.p_hierarchy;
+}
 int orc_debug_amg_certification(long long out[2], int reset) {
     if (!out) return orc::set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
     orc::debug_amg_certification(out, reset != 0);

@@ -127,3 +127,49 @@ def test_partial_sum_grids_have_one_hard_bound(lib):
     assert f(0) == 1 and f(-7) == 1 and f(1) == 1
     assert f(cap - 1) == cap - 1 and f(cap) == cap
     assert f(cap + 1) == cap and f(304 * 8) == cap and f(256 * 40) == cap and f(1 << 40) == cap
+
+
+def restated_schedule(concurrent_momentum, triple_momentum, early_p_hierarchy, partitioned, dbg, profile, gs_slot_space, method, method_p,
+                      reduction_order):
+    """The seven expressions solver_iterate decided its schedule by before the decision became one function (schedule.hpp), restated
+    one to one, and the branch order of the loop body that consumed them."""
+    MULTIGRID, BICGSTAB, JACOBI, MULTICOLOR_GS, BICGSTAB_GS_PRECOND, MULTIGRID_GS, REFERENCE = 2, 3, 1, 16, 17, 18, 1
+    p_multigrid = method_p == MULTIGRID or method_p == MULTIGRID_GS
+    early_p = early_p_hierarchy and p_multigrid and not dbg and not profile
+    lanes_ok = (concurrent_momentum and not partitioned and not dbg and not profile and
+                (method == MULTIGRID or method == BICGSTAB or method == JACOBI or method == MULTIGRID_GS or
+                 method == BICGSTAB_GS_PRECOND or method == MULTICOLOR_GS))
+    lanes_partitioned = concurrent_momentum and partitioned and not dbg and not profile and method == MULTIGRID
+    triple_part = (concurrent_momentum and partitioned and not dbg and not profile and triple_momentum and
+                   (method == MULTIGRID or method == BICGSTAB))
+    triple_ok = (lanes_ok and triple_momentum and reduction_order != REFERENCE and
+                 (method == MULTIGRID or method == BICGSTAB or (method == BICGSTAB_GS_PRECOND and gs_slot_space))) or triple_part
+    p_late = early_p and triple_ok and method == MULTIGRID and method_p == MULTIGRID
+    momentum = 3 if triple_ok else 1 if lanes_ok else 2 if lanes_partitioned else 0   # lock-step, lanes, lanes (partitioned), sequential
+    p_hierarchy = 0 if not early_p else 2 if p_late else 1                            # inside the solve, early, late
+    return momentum + 256 * p_hierarchy
+
+
+def test_schedule_decision_equals_its_restatement_for_every_input(lib):
+    """Every schedule of a SIMPLE iteration computes the same bits (test_stream_scheduling_does_not_change_a_bit), so no test of
+    results can see the DECISION change: it would show as lost speed, or on a partitioned mesh as ranks that issue different
+    collectives.  Here the whole truth table of decide_schedule (orc_amd/csrc/schedule.hpp) through its host-only hook: every
+    combination of the nine boolean inputs and the two reduction orders with every solver type (an unknown one included) for the
+    momentum systems and for the pressure correction."""
+    f = lib.orc_debug_schedule
+    f.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int]
+    f.restype = C.c_int
+    solver_types = [0, 1, 2, 3, 16, 17, 18, 19, 20, 99]
+    seen = set()
+    for switches in range(512):
+        concurrent, triple, early_p, _two_stream, _sibling, partitioned, dbg, profile, gs_slot = [bool(switches >> b & 1) for b in range(9)]
+        for order in (0, 1):
+            for method in solver_types:
+                for method_p in solver_types:
+                    want = restated_schedule(concurrent, triple, early_p, partitioned, dbg, profile, gs_slot, method, method_p, order)
+                    got = f(switches, method, method_p, order)
+                    assert got == want, (switches, order, method, method_p, got, want)
+                    seen.add(got)
+    # every schedule is reachable: four momentum schedules, and the late hierarchy beside the lock-step one only
+    assert {v & 255 for v in seen} == {0, 1, 2, 3} and {v >> 8 for v in seen} == {0, 1, 2}
+    assert {v & 255 for v in seen if v >> 8 == 2} == {3}
