@@ -422,6 +422,46 @@ int orc_surface_integrals(OrcMesh *m, const double *u, const double *v, const do
  * in the mesh's internal face numbering; *n_builds = how often this mesh has built it (stays 1); *chunk = faces per workgroup */
 int orc_mesh_boundary_index(OrcMesh *m, int64_t *zone_ptr, int32_t *faces, int64_t *n_builds, int32_t *chunk);
 
+/* ---------- residual monitors and convergence-controlled runs (new-build extension) ----------
+ * Equation residuals and the mass imbalance of every SIMPLE iteration, a host-side history of them and a stopping rule
+ * (orc_types.h OrcResidual, OrcConvergence; DESIGN.md §3 "Residual monitors" has the definitions and the operator order).
+ * Off by default: a solver that never switches monitoring on launches exactly what it launched before.  Read-only: with monitoring on,
+ * u, v, w, p, the eight report doubles and every later iteration keep their bits.  Fixed association, no float atomics: the same
+ * state gives the same record.
+ *  - orc_solver_set_monitors(s, on): on != 0 allocates the monitor's buffers, clears the history and resets the continuity scale;
+ *    0 frees the buffers and the history.  From then on every iteration of orc_solver_iterate and every inner iteration of
+ *    orc_solver_advance (whose own stopping rule is unchanged) appends one record: one fused pass over the three assembled momentum
+ *    systems with the fields they were assembled from (the residual before the solve), one pass over the right-hand side of the
+ *    pressure correction before its solve, folded on the device and copied with the iteration's last synchronisation.
+ *    On a partitioned mesh the sums and maxima cover the owned rows of all ranks (two collectives per iteration, after the
+ *    iteration's own) and every rank must switch monitoring the same way, before the same iteration.
+ *  - orc_solver_residual_count: records so far.  orc_solver_residual_history: records [first, first + count) into out
+ *    (count * ORC_RESIDUAL_N doubles); a range past the history is ORC_ERR_BAD_ARGUMENT.
+ *  - orc_solver_snapshot / orc_solver_restore do not touch the history or the continuity scale.
+ *  - orc_convergence_check: pure host arithmetic, no device needed.  Returns 1 when every scaled residual (record[16..19]) is <= its
+ *    tolerance and that tolerance is > 0, else 0 (a NaN or infinite residual never converges); *failing_mask (may be NULL) gets bit
+ *    k for equation k (u, v, w, continuity) that fails.  A null or invalid OrcConvergence (negative or NaN tolerance,
+ *    reserved0 != 0) or a null record returns -1 with every bit set.
+ *  - orc_solver_iterate_until: iterations until the check passes, but at least c->min_iterations, and at most max_iterations.
+ *    Needs monitoring on.  report (may be NULL): 8 doubles of the LAST iteration run, laid out as orc_solver_iterate's.
+ *    *iterations_done, *converged: may be NULL.
+ *  - orc_solve_steady_converged: orc_solve_steady with that rule: at most max_iterations iterations; last_record (may be NULL)
+ *    receives the last record.
+ *  - orc_solver_get_pressure_rhs: the right-hand side of the pressure correction as the last iteration (or assembly) left it, in the
+ *    mesh's internal cell order, n_cells doubles; assembles nothing.
+ * All entries but orc_convergence_check look for a device first (ORC_ERR_NO_DEVICE without one, whatever the arguments); then a null
+ * pointer or an invalid struct is ORC_ERR_BAD_ARGUMENT with the solver unchanged. */
+int orc_solver_set_monitors(OrcSolver *s, int32_t on);
+int64_t orc_solver_residual_count(OrcSolver *s);
+int orc_solver_residual_history(OrcSolver *s, uint64_t first, uint64_t count, double *out /*[count * ORC_RESIDUAL_N]*/);
+int orc_convergence_check(const OrcConvergence *c, const double record[ORC_RESIDUAL_N], int32_t *failing_mask);
+int orc_solver_iterate_until(OrcSolver *s, uint64_t max_iterations, const OrcConvergence *c, double *report /*[8]*/,
+                             uint64_t *iterations_done, int32_t *converged);
+int orc_solve_steady_converged(OrcMesh *m, double *u, double *v, double *w, double *p, const OrcSettings *settings, double rho, double mu,
+                               const OrcConvergence *c, uint64_t max_iterations, uint64_t reporting_interval, OrcReportFn report_cb,
+                               void *user, uint64_t *iterations_done, int32_t *converged, double last_record[ORC_RESIDUAL_N]);
+int orc_solver_get_pressure_rhs(OrcSolver *s, double *b_p /*[n_cells]*/);
+
 /* ---------- derived fields, boundary-face maps and VTU export (new-build extension) ----------
  * Opt-in and read-only post-processing of a velocity field where it lives (DESIGN.md §3 "Derived fields and boundary maps").  The
  * compute entries look for a device first (ORC_ERR_NO_DEVICE without one, whatever the arguments); then a null pointer, mask == 0 or
@@ -467,6 +507,9 @@ int orc_bench_bicgstab_iteration(OrcSolver *s, int reps, double *avg_ms);
  * Multigrid arm (two Jacobi scalings, reduction epilogues), timed with HIP events on the library stream.  avg_ms[0], [1]: one
  * system per launch (nu = A p with sum(nu); t = A s with t.s, t.t); avg_ms[2], [3]: u, v, w in one launch (0 when unsupported). */
 int orc_bench_inloop_products(OrcSolver *s, int reps, double avg_ms[4]);
+/* the fused residual pass of the monitors (momentum_residual3_k with its folds) on the solver's assembled momentum systems and
+ * current fields: average ms per pass over `reps`; needs orc_solver_set_monitors */
+int orc_bench_momentum_residuals(OrcSolver *s, int reps, double *avg_ms);
 /* "<narrow>, <scaled>": the last two template arguments of the kernels orc_bench_inloop_products has just launched
  * (spmv_uniform_k<Epi, false, true, narrow, scaled>), so that bench.py names the kernel as a kernel trace does */
 const char *orc_bench_inloop_variant(void);

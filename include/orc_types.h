@@ -251,6 +251,35 @@ enum OrcBoundaryField {
     ORC_BOUNDARY_N = 8
 };
 
+/* Residual monitors (new-build extension; orc_amd.h: orc_solver_set_monitors): one record of ORC_RESIDUAL_N doubles per monitored
+ * SIMPLE iteration.  For a momentum system k in {u, v, w} and an owned row P, with the fields the system was assembled from:
+ * y_P = sum_j a_Pj phi_j (ascending stored order from 0.0, separate multiply and add), r_P = b_P - y_P, d_P = a_PP phi_P (0 without a
+ * stored diagonal).  b_p is the right-hand side of the pressure correction: the cell mass imbalance of the fresh momentum solution.
+ * DESIGN.md §3 "Residual monitors" fixes the operator order and the association of the sums. */
+enum OrcResidual {
+    ORC_RESIDUAL_MOMENTUM_L1 = 0,        /* [0..2] sum |r_P| for u, v, w */
+    ORC_RESIDUAL_MOMENTUM_SCALE = 3,     /* [3..5] sum |d_P| */
+    ORC_RESIDUAL_MOMENTUM_SQ = 6,        /* [6..8] sum r_P^2 */
+    ORC_RESIDUAL_MOMENTUM_MAX = 9,       /* [9..11] max |r_P| */
+    ORC_RESIDUAL_CONTINUITY_L1 = 12,     /* sum |b_p| */
+    ORC_RESIDUAL_CONTINUITY_SQ = 13,     /* sum b_p^2 */
+    ORC_RESIDUAL_CONTINUITY_MAX = 14,    /* max |b_p| */
+    ORC_RESIDUAL_CONTINUITY_SCALE = 15,  /* the largest [12] of the first min(k, 5) monitored iterations since monitoring was switched on */
+    ORC_RESIDUAL_MOMENTUM_SCALED = 16,   /* [16..18] [k] / [3 + k], or [k] itself where the scale is 0 */
+    ORC_RESIDUAL_CONTINUITY_SCALED = 19, /* [12] / [15], or 0 where the scale is 0 */
+    ORC_RESIDUAL_N = 20
+};
+
+/* The stopping rule of orc_solver_iterate_until / orc_solve_steady_converged: converged when each of the four scaled residuals
+ * ([16..19] of a record) is <= its tolerance.  A tolerance of 0 is never met, not even by a residual of exactly 0: that equation
+ * alone keeps the run from stopping early. */
+typedef struct OrcConvergence {
+    double momentum_tolerance[3]; /* >= 0, not NaN: u, v, w */
+    double continuity_tolerance;  /* >= 0, not NaN */
+    uint64_t min_iterations;      /* the check is not made before this many iterations of the call */
+    int32_t reserved0;            /* 0 */
+} OrcConvergence;
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,24 @@ def lib():
             L.orc_write_vtu.restype = C.c_int
             L.orc_write_vtu_faces.argtypes = [C.c_char_p, C.c_int64, _f64, C.c_int64, _i64, _i64, _i64] + _tables
             L.orc_write_vtu_faces.restype = C.c_int
+        # residual monitors and convergence-controlled runs (orc_amd.h "residual monitors"): full signatures
+        if hasattr(L, "orc_solver_set_monitors"):
+            _f64, _u64, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+            L.orc_solver_set_monitors.argtypes = [C.c_void_p, C.c_int32]
+            L.orc_solver_set_monitors.restype = C.c_int
+            L.orc_solver_residual_count.argtypes = [C.c_void_p]
+            L.orc_solver_residual_count.restype = C.c_int64
+            L.orc_solver_residual_history.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, _f64]
+            L.orc_solver_residual_history.restype = C.c_int
+            L.orc_convergence_check.argtypes = [C.c_void_p, _f64, _i32]
+            L.orc_convergence_check.restype = C.c_int
+            L.orc_solver_iterate_until.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, _f64, _u64, _i32]
+            L.orc_solver_iterate_until.restype = C.c_int
+            L.orc_solve_steady_converged.argtypes = [C.c_void_p, _f64, _f64, _f64, _f64, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                                     C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, _u64, _i32, _f64]
+            L.orc_solve_steady_converged.restype = C.c_int
+            L.orc_solver_get_pressure_rhs.argtypes = [C.c_void_p, _f64]
+            L.orc_solver_get_pressure_rhs.restype = C.c_int
         # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
         if hasattr(L, "orc_debug_amg_setup_stats"):
             L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]

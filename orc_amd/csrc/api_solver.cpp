@@ -6,6 +6,7 @@
 #include <memory>
 
 #include "assembly.hpp"
+#include "convergence.hpp"
 
 using namespace orc;
 
@@ -22,6 +23,27 @@ int download_csr_values(OrcMesh &m, const DevBuf<double> &sell, double *host_val
     return tmp.download(host_vals, (size_t)m.pat.nnz);
 }
 
+}  // namespace
+
+namespace {
+// SIMPLE iterations until the last record passes the check (not before c.min_iterations) or max_iterations are through; rep (8
+// doubles, may be null) keeps the last iteration's report, each(it) is called after iteration `it` (counted from 1)
+template <class Each>
+int iterate_until(SolverState &st, uint64_t max_iterations, const OrcConvergence &c, double *rep, uint64_t *done, int32_t *converged, Each &&each) {
+    uint64_t it = 0;
+    int32_t ok = 0;
+    int status = ORC_OK;
+    while (it < max_iterations && !ok && status == ORC_OK) {
+        status = solver_iterate(st, 1, rep);
+        if (status != ORC_OK) break;
+        ++it;
+        each(it);
+        if (it >= c.min_iterations) ok = convergence_check(c, st.mon.history.data() + st.mon.history.size() - ORC_RESIDUAL_N, nullptr);
+    }
+    if (done) *done = it;
+    if (converged) *converged = ok;
+    return status;
+}
 }  // namespace
 
 extern "C" {
@@ -238,6 +260,57 @@ int orc_solver_iterate(OrcSolver *s, uint64_t iterations, double *report) {
     const int st = solver_iterate(s->st, iterations, report);
     note.leave(st);
     return st;
+}
+
+// ---------------------------------------------------------------- convergence-controlled runs (OrcConvergence, residuals.hip)
+static_assert(sizeof(OrcConvergence) == 48 && offsetof(OrcConvergence, momentum_tolerance) == 0 && offsetof(OrcConvergence, continuity_tolerance) == 24 &&
+                  offsetof(OrcConvergence, min_iterations) == 32 && offsetof(OrcConvergence, reserved0) == 40,
+              "OrcConvergence is part of the ABI (orc_amd/settings.py Convergence mirrors it)");
+static_assert(ORC_RESIDUAL_N == 20, "the record layout is part of the ABI (orc_amd/solver.py RESIDUAL_NAMES)");
+
+int orc_solver_iterate_until(OrcSolver *s, uint64_t max_iterations, const OrcConvergence *c, double *report, uint64_t *iterations_done,
+                             int32_t *converged) {
+    ORC_TRY(ensure_init());
+    if (!s || !c) return set_error(ORC_ERR_BAD_ARGUMENT, "iterate_until: null argument");
+    if (!convergence_valid(*c)) return set_error(ORC_ERR_BAD_ARGUMENT, "iterate_until: tolerances must be >= 0 and reserved0 must be 0");
+    if (!s->st.mon.on) return set_error(ORC_ERR_BAD_ARGUMENT, "iterate_until without orc_solver_set_monitors");
+    GuardNote note;
+    const int st = iterate_until(s->st, max_iterations, *c, report, iterations_done, converged, [](uint64_t) {});
+    note.leave(st);
+    return st;
+}
+
+int orc_solve_steady_converged(OrcMesh *m, double *u, double *v, double *w, double *p, const OrcSettings *settings, double rho, double mu,
+                               const OrcConvergence *c, uint64_t max_iterations, uint64_t reporting_interval, OrcReportFn report_cb, void *user,
+                               uint64_t *iterations_done, int32_t *converged, double *last_record) {
+    ORC_TRY(ensure_init());
+    if (!m || !settings || !u || !v || !w || !p || !c) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
+    if (!convergence_valid(*c)) return set_error(ORC_ERR_BAD_ARGUMENT, "solve_steady_converged: tolerances must be >= 0 and reserved0 must be 0");
+    int st = ORC_OK;
+    OrcSolver *s = orc_solver_create(m, settings, rho, mu, &st);
+    if (!s) return st;
+    std::unique_ptr<OrcSolver> guard(s);
+    ORC_TRY(orc_solver_set_fields(s, u, v, w, p));
+    ORC_TRY(monitors_enable(s->st, true));
+    GuardNote note;
+    auto start = std::chrono::steady_clock::now();
+    double rep[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
+    st = iterate_until(s->st, max_iterations, *c, rep, iterations_done, converged, [&](uint64_t it) {
+        if (!(report_cb && reporting_interval > 0 && it % reporting_interval == 0)) return;
+        auto now = std::chrono::steady_clock::now();
+        double ms = std::chrono::duration<double, std::milli>(now - start).count() / (double)reporting_interval;
+        start = now;
+        report_cb(it, rep, rep + 3, rep[6], rep[7], ms, user);
+    });
+    if (last_record) {
+        const std::vector<double> &h = s->st.mon.history;
+        if (h.empty()) std::fill(last_record, last_record + ORC_RESIDUAL_N, 0.);
+        else std::copy(h.end() - ORC_RESIDUAL_N, h.end(), last_record);
+    }
+    if (st == ORC_OK) st = post_loop_gradients_dev(s->st);  // as orc_solve_steady
+    int st2 = orc_solver_get_fields(s, u, v, w, p);
+    note.leave(st != ORC_OK ? st : st2);
+    return st != ORC_OK ? st : st2;
 }
 
 int orc_solver_snapshot(OrcSolver *s) {

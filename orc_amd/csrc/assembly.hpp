@@ -173,6 +173,20 @@ struct SolverState {
     double snap_time = 0.;
     bool snap_transient = false;
     bool diagonals_assembled = false;  // k_momentum has written du/dv/dw at least once (Rhie-Chow face fluxes need them)
+    // Residual monitors (orc_solver_set_monitors, residuals.hip): off unless enabled.  The partial sums and the folded raw slots are
+    // the monitor's own — s.partials / s.scal belong to the Peclet statistics and the correction.  dev: the folded slots in
+    // COLLECTIVE order (kSums sums, then kMaxima maxima: one all-reduce each); raw: pinned host memory where the iteration's copy of
+    // them lands (complete at the iteration's last synchronisation).
+    struct Monitor {
+        static constexpr int kSums = 11, kMaxima = 4;  // sum|r|, sum|d|, sum r^2 x 3, sum|b_p|, sum b_p^2; max|r| x 3, max|b_p|
+        bool on = false;
+        DevBuf<double> partials;   // [12 * kMaxPartials] momentum pass, then [3 * kMaxPartials] imbalance pass
+        DevBuf<double> dev;        // [kSums + kMaxima]
+        double *raw = nullptr;     // [kSums + kMaxima], hipHostMalloc
+        std::vector<double> history;  // ORC_RESIDUAL_N doubles per monitored iteration
+        uint64_t seen = 0;         // monitored iterations since monitoring was switched on
+        double scale = 0.;         // the continuity scale (record slot 15)
+    } mon;
     // Passive scalar transport (orc_solver_set_scalar, scalar.hip): off unless enabled; every buffer is the arm's own, so
     // that nothing the flow reads is written.
     struct Scalar {
@@ -261,6 +275,15 @@ int surface_report_dev(OrcMesh &m, const double *u, const double *v, const doubl
                        const double origin[3], double *per_zone);
 // the boundary index of the mesh (m.surface), built at first use: what the reports and the boundary maps of derived.hip walk
 int surface_index(OrcMesh &m);
+// residual monitors (residuals.hip), all asynchronous on ctx().stream: the fused pass over a_u/a_v/a_w, b_u/b_v/b_w and the fields they
+// were assembled from (after k_momentum, before the solves); the pass over b_p (after k_pressure_correction, before the p' solve);
+// the all-reduces of a partitioned mesh and the copy of the fifteen raw slots into s.mon.raw (complete at the iteration's last
+// synchronisation); the record of the iteration from s.mon.raw, appended to the history.
+int monitors_enable(SolverState &s, bool on);
+int k_momentum_residuals(SolverState &s);
+int k_imbalance(SolverState &s);
+int monitor_fetch(SolverState &s);
+void monitor_append(SolverState &s);
 
 }  // namespace orc
 

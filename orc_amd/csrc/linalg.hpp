@@ -333,6 +333,7 @@ int bench_inloop_products3_dev(const MatView3 &A, const double *x3, double *y3, 
 // from `arena`: A.val = s2 * (s1 * val), A.s1 = A.s2 = null — the same numbers the product kernels would form entry by entry, 16
 // (one system) / 48 (three systems) fewer bytes per row and product.  No-op when the view has no scaling or no known size.
 int matview_stream_nt(const MatView &A);  // the cache policy launch_spmv picks for this view's matrix streams (MatView::nt)
+int stream_nt_policy(int64_t stream_bytes);  // the same decision for a launch that streams `stream_bytes` of matrix data once (ORC_SPMV_NT included)
 int materialize_scaled_view(MatView &A, uint64_t iteration_count, Arena &arena);
 int materialize_scaled_view3(MatView3 &A, uint64_t iteration_count, Arena &arena);
 // A matrix seen through one more Jacobi scaling (linear_algebra.rs:159-166), prepared ONCE for several BiCGSTAB solves on it: the

@@ -422,6 +422,7 @@ int solver_iterate(SolverState &s, uint64_t iterations, double *report) {
         ORC_TRY(exchange_gradient(s, s.gp.p));
         ORC_TRY(k_face_flux(s, true));
         ORC_TRY(k_momentum(s, report ? peclet : nullptr));       // :61-82
+        if (s.mon.on) ORC_TRY(k_momentum_residuals(s));          // the residuals before the solve: u, v, w are still the fields of the assembly
         if (H.active()) { double *d3[3] = {s.du.p, s.dv.p, s.dw.p}; ORC_TRY(H.exchange(d3, 3)); }
         if (dbg) { debug_field(s, "b_u", s.b_u); debug_field(s, "b_v", s.b_v); debug_field(s, "b_w", s.b_w); }
         const OrcSettings p_set = s.p_settings();   // the pressure correction's: the settings, or orc_solver_set_pressure_solver's override
@@ -479,6 +480,7 @@ int solver_iterate(SolverState &s, uint64_t iterations, double *report) {
         ORC_TRACE("p' set-up joined");
         if (H.active()) { double *f[3] = {s.u.p, s.v.p, s.w.p}; ORC_TRY(H.exchange(f, 3)); }
         ORC_TRY(k_pressure_correction(s));                       // :137-148 (the matrix comes out as in the early pass)
+        if (s.mon.on) ORC_TRY(k_imbalance(s));                   // b_p: the mass imbalance of the fresh momentum solution
         ORC_TRY(vec_fill(s.p_prime.p, 0., s.n));                 // :167
         if (dbg) debug_field(s, "b_p", s.b_p);
         ORC_TRACE("p' solve");
@@ -499,8 +501,10 @@ int solver_iterate(SolverState &s, uint64_t iterations, double *report) {
             r[6] = std::sqrt(sums[1]); r[7] = std::sqrt(sums[0]);
         }
         int st = 0;
+        if (s.mon.on) ORC_TRY(monitor_fetch(s));  // behind every collective of the iteration; its copy is complete at the synchronisation below
         ORC_HIP(hipMemcpyAsync(&st, s.dev_status.p, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
         ORC_HIP(hipStreamSynchronize(ctx().stream));
+        if (s.mon.on) monitor_append(s);
         if (H.active()) st = comm_global_status(st);
         if (st) return st;
         if (std::isnan(u_avg) || std::isnan(v_avg) || std::isnan(w_avg)) return ORC_ERR_SOLUTION_DIVERGED;  // :217-221

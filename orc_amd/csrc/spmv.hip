@@ -23,6 +23,7 @@ static inline int stream_nt(int64_t stream_bytes) {
     return stream_bytes > ((int64_t)128 << 20);
 }
 
+int stream_nt_policy(int64_t stream_bytes) { return stream_nt(stream_bytes); }
 int matview_stream_nt(const MatView &A) { return stream_nt(A.pk.ptr && A.xw.lidx ? A.pk.total * 10 : A.P.padded * (A.P.col16 ? 10 : 12)); }
 
 int spmv_grid(int32_t n_slices) {

@@ -67,6 +67,22 @@ class LinearSolver(C.Structure):
     ]
 
 
+class Convergence(C.Structure):
+    """OrcConvergence: the stopping rule of Solver.iterate_until / solve_steady_converged — converged when each scaled residual
+    (record slots 16..19: u, v, w, continuity) is <= its tolerance; a tolerance of 0 is never met."""
+    _fields_ = [
+        ("momentum_tolerance", C.c_double * 3), ("continuity_tolerance", C.c_double), ("min_iterations", C.c_uint64),
+        ("reserved0", C.c_int32),
+    ]
+
+    @classmethod
+    def make(cls, momentum=1e-4, continuity=1e-4, min_iterations=0):
+        """momentum: one tolerance for u, v, w or three of them"""
+        m = [float(momentum)] * 3 if not hasattr(momentum, "__len__") else [float(x) for x in momentum]
+        return cls(momentum_tolerance=(C.c_double * 3)(*m), continuity_tolerance=float(continuity), min_iterations=int(min_iterations),
+                   reserved0=0)
+
+
 class TimeScheme:  # include/orc_types.h OrcTimeScheme
     Euler, BDF2 = 0, 1
 

@@ -36,6 +36,42 @@ def solve_steady(mesh, u, v, w, p, numerical_settings, rho, mu, iteration_count,
     return st
 
 
+# orc_types.h OrcResidual: the twenty doubles of a residual record (Solver.residual_history), by slot
+RESIDUAL_NAMES = ("l1_u", "l1_v", "l1_w", "scale_u", "scale_v", "scale_w", "sq_u", "sq_v", "sq_w", "max_u", "max_v", "max_w",
+                  "continuity_l1", "continuity_sq", "continuity_max", "continuity_scale", "scaled_u", "scaled_v", "scaled_w",
+                  "scaled_continuity")
+_RESIDUAL_N = len(RESIDUAL_NAMES)  # ORC_RESIDUAL_N
+
+
+def convergence_check(convergence, record):
+    """orc_convergence_check (host arithmetic, no device): (converged, failing_mask) of one residual record under a
+    settings.Convergence; bit k of the mask = equation k (u, v, w, continuity) fails.  converged is -1 for an invalid rule."""
+    rec = _f64(record).reshape(_RESIDUAL_N)
+    mask = C.c_int32(0)
+    ok = lib().orc_convergence_check(C.byref(convergence) if convergence is not None else None, _p(rec), C.byref(mask))
+    return ok, mask.value
+
+
+def solve_steady_converged(mesh, u, v, w, p, numerical_settings, rho, mu, convergence, max_iterations, reporting_interval=0,
+                           report=None, raise_on_error=True):
+    """orc_solve_steady_converged: solve_steady that stops once `convergence` (settings.Convergence) is met, after at most
+    max_iterations; u, v, w, p are updated in place -> (status, iterations used, converged, last residual record)."""
+    for a in (u, v, w, p):
+        assert a.dtype == np.float64 and a.flags.c_contiguous and len(a) == mesh.n_cells
+    cb = None
+    if report is not None:
+        def _cb(it, mv, pe, vc, pc, ms, _user):
+            report(it, (mv[0], mv[1], mv[2]), (pe[0], pe[1], pe[2]), vc, pc, ms)
+        cb = _REPORT_FN(_cb)
+    done, conv, rec = C.c_uint64(0), C.c_int32(0), np.zeros(_RESIDUAL_N)
+    st = lib().orc_solve_steady_converged(mesh.ptr, _p(u), _p(v), _p(w), _p(p), C.byref(numerical_settings), C.c_double(rho),
+                                          C.c_double(mu), C.byref(convergence), C.c_uint64(max_iterations),
+                                          C.c_uint64(reporting_interval), cb, None, C.byref(done), C.byref(conv), _p(rec))
+    if raise_on_error:
+        check(st)
+    return st, int(done.value), bool(conv.value), rec
+
+
 def solve_transient(mesh, u, v, w, p, settings, rho, mu, transient, time_steps, reporting_interval=0, report=None,
                     raise_on_error=True):
     """Implicit time stepping (orc_solve_transient): time_steps steps of `transient` (settings.Transient) from u, v, w, p,
@@ -253,6 +289,45 @@ class Solver:
             check(st)
         return (st, rep) if report else st
 
+    # ---------------------------------------------------------------- residual monitors (orc_solver_set_monitors)
+    def set_monitors(self, on=True, raise_on_error=True):
+        """orc_solver_set_monitors: from now on every iterate() and every inner iteration of advance() appends one residual record;
+        switching on clears the history and resets the continuity scale, switching off frees the monitor.  Reads only: fields and
+        reports keep their bits.  On a partitioned mesh every rank switches the same way."""
+        st = lib().orc_solver_set_monitors(self.ptr, C.c_int32(1 if on else 0))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def residual_history(self, first=0, count=None):
+        """the residual records [first, first + count) -> an array (k, 20), columns as RESIDUAL_NAMES (count=None: all from first)"""
+        have = int(lib().orc_solver_residual_count(self.ptr))
+        if count is None:
+            count = max(have - first, 0)
+        out = np.zeros((count, _RESIDUAL_N))
+        check(lib().orc_solver_residual_history(self.ptr, C.c_uint64(first), C.c_uint64(count), _p(out)))
+        return out
+
+    def iterate_until(self, max_iterations, convergence, report=False, raise_on_error=True):
+        """orc_solver_iterate_until: SIMPLE iterations until `convergence` (settings.Convergence) is met, not before its
+        min_iterations and at most max_iterations; needs set_monitors() -> (status, iterations done, converged), with report=True
+        also the 8 report values of the last iteration"""
+        rep = np.zeros(8) if report else None
+        done, conv = C.c_uint64(0), C.c_int32(0)
+        st = lib().orc_solver_iterate_until(self.ptr, C.c_uint64(max_iterations), C.byref(convergence) if convergence is not None else None,
+                                            _p(rep) if report else None, C.byref(done), C.byref(conv))
+        if raise_on_error:
+            check(st)
+        res = (st, int(done.value), bool(conv.value))
+        return res + (rep,) if report else res
+
+    def pressure_rhs(self):
+        """orc_solver_get_pressure_rhs: the right-hand side of the pressure correction as the last iteration left it (the cell mass
+        imbalance of its momentum solution), the mesh's internal cell order; assembles nothing"""
+        b = np.zeros(self.n)
+        check(lib().orc_solver_get_pressure_rhs(self.ptr, _p(b)))
+        return b
+
     def set_transient(self, transient=None, raise_on_error=True):
         """orc_solver_set_transient: a settings.Transient turns implicit time stepping on (0 known levels), None turns it off"""
         st = lib().orc_solver_set_transient(self.ptr, C.byref(transient) if transient is not None else None)
@@ -455,6 +530,12 @@ class Solver:
         lib().orc_bench_inloop_variant.restype = C.c_char_p
         self.inloop_variant = lib().orc_bench_inloop_variant().decode()  # "<narrow>, <scaled>, <non-temporal>" template arguments of those launches
         return [ms[k] for k in range(4)]
+
+    def bench_momentum_residuals(self, reps=50):
+        """orc_bench_momentum_residuals: ms per fused residual pass over the assembled momentum systems (needs set_monitors())"""
+        ms = C.c_double(0.0)
+        check(lib().orc_bench_momentum_residuals(self.ptr, C.c_int(reps), C.byref(ms)))
+        return ms.value
 
     def bench_gs_sweep0(self, reps=50):
         """orc_bench_gs_sweep0: (ms per sweep-from-zero of one system, ms per sweep of u, v, w in one launch per colour, colours)"""
