@@ -6,10 +6,11 @@
 //   ORC_SOLVER_MULTICOLOR_GS        iteration_count sweeps of the reference's row update (:225-239) in colour order,
 //   ORC_SOLVER_BICGSTAB_GS_PRECOND  the reference's BiCGSTAB recurrences, right-preconditioned by one GS sweep,
 //   ORC_SOLVER_MULTIGRID_GS         the Multigrid arm with GS sweeps as its smoother (amg_cycle.hip).
-// Rows of one colour share no matrix entry, so a colour is one fully parallel kernel and the sweep is a true
-// Gauss-Seidel in colour order; the row sum runs in ascending-column order like everything else.
+// The colouring is proper on the pattern of A united with its transpose: no stored a_ij or a_ji joins two rows of one
+// colour, whether or not the pattern is structurally symmetric.  So a colour is one fully parallel kernel and the sweep
+// is a true Gauss-Seidel in colour order; the row sum runs in ascending-column order like everything else.
 // Colouring: speculative first-fit with conflict resolution by a deterministic hash priority (64-bit colour mask), on
-// the device; the one-class-per-round Jones-Plassmann variant is kept behind ORC_GS_JONES_PLASSMANN=1.
+// the device.
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -69,18 +70,26 @@ __device__ __forceinline__ bool prio_greater(int a, int b) {  // strict total or
 
 __device__ __forceinline__ int64_t row_base_sell(const SellDev &P, int64_t i) { return P.slice_ptr[i >> 6] + (i & 63); }
 
-// Speculative first-fit colouring with conflict resolution (Gebremedhin-Manne), two kernels per round, Jacobi style so
+// Speculative first-fit colouring with conflict resolution (Gebremedhin-Manne), three kernels per round, Jacobi style so
 // that the result does not depend on scheduling: every uncoloured row takes the smallest colour none of its neighbours
 // holds in the previous round's state (tentative), then a row that shares its tentative colour with a neighbour coloured
 // in the same round gives it up if the neighbour has the higher priority.  A handful of rounds whatever the row
 // lengths, where one Jones-Plassmann colour per round needs ~160 rounds on the coarse AMG levels (150 neighbours).
-__global__ void spec_assign_k(SellDev P, const int *__restrict__ color_in, int *__restrict__ color_out, int *__restrict__ overflow) {
+// The pattern need not be structurally symmetric: a row j whose column sits in row i's line while i's does not sit in
+// j's never sees i, so the row that does see the pair settles it for both.  Where both are new this round the one of
+// lower priority loses — i by itself as ever, j through a store to its flag; where i is final already, j loses and
+// i's colour enters j's forbidden mask, which the assignment adds to the colours in use (without it j would choose the
+// same colour again in every round).  The stores are idempotent and the mask is an OR, so the outcome still does not
+// depend on scheduling; on a symmetric pattern they only repeat what j finds by itself, and the colouring is bit for
+// bit the one of the two-kernel form that looked at a row's own line alone.
+__global__ void spec_assign_k(SellDev P, const int *__restrict__ color_in, const unsigned long long *__restrict__ forbid, int *__restrict__ color_out,
+                              int *__restrict__ overflow) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P.n; i += (int64_t)gridDim.x * blockDim.x) {
         const int ci = color_in[i];
         if (ci >= 0) { color_out[i] = ci; continue; }
         const int len = P.row_len[i];
         const int64_t base = row_base_sell(P, i);
-        unsigned long long used = 0ull;
+        unsigned long long used = forbid[i];
         for (int k = 0; k < len; ++k) {
             const int j = P.col[base + (int64_t)k * 64];
             if (j == i || j >= P.n) continue;
@@ -92,23 +101,37 @@ __global__ void spec_assign_k(SellDev P, const int *__restrict__ color_in, int *
         color_out[i] = __ffsll((long long)freec) - 1;
     }
 }
-// color_prev: state before this round (-1 = was uncoloured), color_tent: after the tentative assignment; the outcome
-// goes to a third array, so every row sees the same tentative state whatever the scheduling.
-__global__ void spec_resolve_k(SellDev P, const int *__restrict__ color_prev, const int *__restrict__ color_tent, int *__restrict__ color_out,
-                               int *__restrict__ remaining) {
+// color_prev: state before this round (-1 = was uncoloured), color_tent: after the tentative assignment; the verdicts go
+// to the flags (zero on entry), so every row sees the same tentative state whatever the scheduling.  Final rows scan
+// their lines too: they are the only ones that see a new row which does not store them.
+__global__ void spec_resolve_k(SellDev P, const int *__restrict__ color_prev, const int *__restrict__ color_tent, int *__restrict__ lose,
+                               unsigned long long *__restrict__ forbid) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P.n; i += (int64_t)gridDim.x * blockDim.x) {
         const int ci = color_tent[i];
-        if (color_prev[i] >= 0 || ci < 0) { color_out[i] = ci; if (ci < 0) atomicAdd(remaining, 1); continue; }
+        if (ci < 0) continue;  // (overflow: the round ends in an error)
+        const bool final_i = color_prev[i] >= 0;
         const int len = P.row_len[i];
         const int64_t base = row_base_sell(P, i);
-        bool lose = false;
-        for (int k = 0; k < len && !lose; ++k) {
+        bool lost = false;
+        for (int k = 0; k < len; ++k) {
             const int j = P.col[base + (int64_t)k * 64];
             if (j == i || j >= P.n) continue;
-            if (color_prev[j] < 0 && color_tent[j] == ci && prio_greater(j, (int)i)) lose = true;
+            if (color_prev[j] >= 0 || color_tent[j] != ci) continue;
+            // j is new this round and took i's colour
+            if (final_i) { lose[j] = 1; atomicOr(&forbid[j], 1ull << ci); }
+            else if (prio_greater(j, (int)i)) lost = true;
+            else lose[j] = 1;
         }
-        color_out[i] = lose ? -1 : ci;
-        if (lose) atomicAdd(remaining, 1);
+        if (lost) lose[i] = 1;
+    }
+}
+// the round's outcome, in place: a new row keeps its tentative colour unless it was flagged; the flags are left zero
+__global__ void spec_commit_k(int64_t n, int *__restrict__ color, const int *__restrict__ color_tent, int *__restrict__ lose, int *__restrict__ remaining) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (color[i] >= 0) continue;
+        const int ci = color_tent[i];
+        if (lose[i] || ci < 0) { lose[i] = 0; atomicAdd(remaining, 1); continue; }
+        color[i] = ci;
     }
 }
 
@@ -128,40 +151,44 @@ static int build_coloring(const SellDev &P, Coloring &C, Arena *arena = nullptr,
     const int64_t n = P.n;
     const size_t nn = (size_t)std::max<int64_t>(n, 1);
     hipStream_t st = ctx().stream;
-    DevBuf<int> tmp_b, tent_b, flags_b, counts_b;
-    int *tmp, *tent, *flags, *counts;
+    DevBuf<int> lose_b, tent_b, flags_b, counts_b;
+    DevBuf<unsigned long long> forbid_b;
+    int *lose, *tent, *flags, *counts;
+    unsigned long long *forbid;
     if (arena) {  // per-solve colouring: no hipMalloc / hipFree inside the SIMPLE loop
         ORC_TRY(arena->alloc(nn, &C.color_p));
         ORC_TRY(arena->alloc(nn, &C.rows_p));
-        ORC_TRY(arena->alloc(nn, &tmp));
+        ORC_TRY(arena->alloc(nn, &lose));
         ORC_TRY(arena->alloc(nn, &tent));
+        ORC_TRY(arena->alloc(nn, &forbid));
         ORC_TRY(arena->alloc((size_t)2, &flags));
         ORC_TRY(arena->alloc((size_t)128, &counts));
     } else {
         ORC_TRY(C.color.alloc(nn));
         ORC_TRY(C.rows.alloc(nn));
-        ORC_TRY(tmp_b.alloc(nn));
+        ORC_TRY(lose_b.alloc(nn));
         ORC_TRY(tent_b.alloc(nn));
+        ORC_TRY(forbid_b.alloc(nn));
         ORC_TRY(flags_b.alloc(2));
         ORC_TRY(counts_b.alloc(128));
-        C.color_p = C.color.p; C.rows_p = C.rows.p; tmp = tmp_b.p; tent = tent_b.p; flags = flags_b.p; counts = counts_b.p;
+        C.color_p = C.color.p; C.rows_p = C.rows.p; lose = lose_b.p; tent = tent_b.p; forbid = forbid_b.p; flags = flags_b.p; counts = counts_b.p;
     }
     ORC_HIP(hipMemsetAsync(C.color_p, 0xff, sizeof(int) * (size_t)n, st));
-    int *in = C.color_p, *out = tmp;
+    ORC_HIP(hipMemsetAsync(lose, 0, sizeof(int) * (size_t)n, st));
+    ORC_HIP(hipMemsetAsync(forbid, 0, sizeof(unsigned long long) * (size_t)n, st));
     const int g = grid_for(n);
     for (int round = 0; round < 10000; ++round) {
         ORC_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), st));
-        hipLaunchKernelGGL(spec_assign_k, dim3(g), dim3(kBlock), 0, st, P, in, tent, flags + 1);
-        hipLaunchKernelGGL(spec_resolve_k, dim3(g), dim3(kBlock), 0, st, P, in, tent, out, flags);
+        hipLaunchKernelGGL(spec_assign_k, dim3(g), dim3(kBlock), 0, st, P, C.color_p, forbid, tent, flags + 1);
+        hipLaunchKernelGGL(spec_resolve_k, dim3(g), dim3(kBlock), 0, st, P, C.color_p, tent, lose, forbid);
+        hipLaunchKernelGGL(spec_commit_k, dim3(g), dim3(kBlock), 0, st, n, C.color_p, tent, lose, flags);
         ORC_HIP(hipGetLastError());
         int h[2];
         ORC_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st));
         ORC_HIP(hipStreamSynchronize(st));
-        std::swap(in, out);
         if (h[1]) return set_error(ORC_ERR_BAD_ARGUMENT, "colouring needs more than 64 colours");
         if (h[0] == 0) break;
     }
-    if (in != C.color_p) ORC_HIP(hipMemcpyAsync(C.color_p, in, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, st));
     ORC_HIP(hipMemsetAsync(counts, 0, 128 * sizeof(int), st));
     hipLaunchKernelGGL(color_count_k, dim3(g), dim3(kBlock), 0, st, C.color_p, n, counts);
     int hc[64];
@@ -1002,7 +1029,7 @@ int gs_bicgstab3_dev(const MatView A[3], const double *const b[3], double *const
     const Coloring *C = nullptr;
     ArenaScope scope(arena);
     ORC_TRY(get_coloring(A[0], owned, &C, &arena));
-    if (!C->sorted.built) return set_error(ORC_ERR_BAD_ARGUMENT, "gs_bicgstab3_dev: no colour-sorted layout (ORC_GS_SORTED=0?)");
+    if (!C->sorted.built) return set_error(ORC_ERR_BAD_ARGUMENT, "gs_bicgstab3_dev: no colour-sorted layout");
     int *status;
     ORC_TRY(arena.alloc((size_t)1, &status));
     ORC_HIP(hipMemsetAsync(status, 0, sizeof(int), st));

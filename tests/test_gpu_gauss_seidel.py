@@ -179,3 +179,35 @@ def test_gs_momentum_systems_in_lock_step_are_bit_identical_to_their_own_solves(
         assert np.isfinite(out[0][0]).all()
         for x, y in zip(*out):
             assert np.array_equal(x, y), shape
+
+
+def test_gs_momentum_systems_in_lock_step_off_the_hex_channel(gpu, oracle, mesh_path, monkeypatch):
+    """The same comparison on the prism / hex checker mesh (meshgen.write_mixed_channel_msh(path, 6, 4, 3, split="checker")): rows of 4, 5
+    and 6 neighbours in one pattern, and every colour has fewer than 64 rows, so every slice of the host-built colour-sorted layout
+    (build_color_sell) is partly padding — the slots whose rowid is -1 take part in every launch of the lock-step solve."""
+    import helpers as H
+    import scipy.sparse as sp
+    from orc_amd.linear_algebra import debug_coloring
+    from orc_amd.settings import NumericalSettings
+    from orc_amd.solver import solve_steady
+    from test_gpu_assembly import make_named
+    _, dm, a = make_named(oracle, mesh_path, "prism_hex")
+    rp, ci = dm.matrix_pattern()
+    n = len(rp) - 1
+    pattern = sp.csr_matrix((np.ones(len(ci)), ci, rp), shape=(n, n))
+    colors, nc = debug_coloring(pattern)
+    counts = np.bincount(colors, minlength=nc)
+    assert len(set(np.diff(rp).tolist())) > 1, "prisms and hexahedra: rows of different lengths"
+    assert (counts > 0).all() and (counts < 64).all(), counts
+    s = NumericalSettings.default(momentum=4, solver_type=BICGSTAB_GS, iterations=12)
+    out = []
+    for triple in ("1", "0"):
+        monkeypatch.setenv("ORC_TRIPLE_MOMENTUM", triple)
+        u, v, w, p = H.seeded_fields(a, seed=8, scale_u=4e-4)
+        solve_steady(dm, u, v, w, p, s, 1000.0, 1e-3, 3)
+        out.append((u, v, w, p))
+    for x in out[0]:
+        assert np.isfinite(x).all()
+    assert not np.array_equal(out[0][0], H.seeded_fields(a, seed=8, scale_u=4e-4)[0])
+    for x, y in zip(*out):
+        assert np.array_equal(x.view(np.uint64), y.view(np.uint64))
