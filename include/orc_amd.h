@@ -412,8 +412,8 @@ int orc_solver_scalar_boundary_flux(OrcSolver *s, double *per_zone);
  * device first (ORC_ERR_NO_DEVICE without one, whatever the arguments); then a non-finite origin, a null solver / mesh / field /
  * output, and for orc_surface_integrals a non-finite or non-positive rho or mu, are ORC_ERR_BAD_ARGUMENT. */
 /* per zone ORC_SURFACE_N doubles (orc_types.h OrcSurfaceQuantity), zone index as orc_mesh_update_zones uses it.
- * origin: reference point of MOMENT, NULL = (0,0,0).  Uses the solver's current u, v, w, p, rho, mu and the mesh's
- * current zone table; changes no bit of the solver.  On a partitioned mesh every rank calls it and receives the global sums. */
+ * origin: reference point of MOMENT, NULL = (0,0,0).  Uses the solver's current u, v, w, p, rho, mu (with variable viscosity on: the
+ * viscosity of the face's cell, see "variable viscosity" below) and the mesh's current zone table; changes no bit of the solver.  On a partitioned mesh every rank calls it and receives the global sums. */
 int orc_solver_surface_report(OrcSolver *s, const double origin[3], double *per_zone /*[n_zones * ORC_SURFACE_N]*/);
 /* the same on host fields in ORC cell order (post-processing a read_data file): uploads, reports, frees */
 int orc_surface_integrals(OrcMesh *m, const double *u, const double *v, const double *w, const double *p,
@@ -494,6 +494,43 @@ int orc_write_vtu(const char *path, int64_t n_points, const double *points /*[3V
 int orc_write_vtu_faces(const char *path, int64_t n_points, const double *points, int64_t n_faces, const int64_t *face_ids,
                         const int64_t *face_node_ptr, const int64_t *face_nodes, int32_t n_arrays, const char *const *names,
                         const int32_t *components, const double *const *data, int32_t encoding);
+
+/* ---------- variable viscosity (new-build extension, orc_types.h OrcViscosity) ----------
+ * A per-cell viscosity in the momentum diffusion: a prescribed field, or a power-law, Carreau or Smagorinsky law of the strain-rate
+ * magnitude (DESIGN.md §3 "Variable viscosity" has the definitions and the operator order).  Off by default: a solver that never calls
+ * orc_solver_set_viscosity* launches exactly what it launched before and allocates nothing new.  The momentum assembly, Rhie-Chow and
+ * the solves are untouched: two passes ahead of them evaluate the law per cell and rebuild the diffusion matrix a_di and its wall
+ * terms b_u_di, b_v_di, b_w_di with a face viscosity.  The momentum equation keeps its Laplacian form div(mu grad U); the transpose
+ * part div(mu (grad U)^T) is not added.
+ *  - orc_solver_set_viscosity(s, c): checks c, then evaluates the law on the current fields (no relaxation) and rebuilds a_di at
+ *    once.  From then on every SIMPLE iteration and every orc_solver_assemble_momentum re-evaluates the law on its fresh fields (not
+ *    for FIELD), exchanges the ghost viscosities of a partitioned mesh and rebuilds a_di before the momentum assembly.  The first of
+ *    these evaluations takes the law's value itself; later ones are relaxed with c->relaxation.  c == NULL turns the arm off, frees
+ *    its buffers and puts the constant-mu a_di, b_*_di back, bit for bit.
+ *  - orc_solver_set_viscosity_field: the FIELD model's data, n_cells doubles in ORC cell order (on a partitioned mesh the rank's
+ *    array, ghost entries included), every entry > 0 and finite.  May be called before the model is selected; with FIELD on, a_di is
+ *    rebuilt at once.
+ *  - orc_solver_get_viscosity: the field the last assembly used (the constant mu while the arm is off), cell order as
+ *    orc_solver_get_fields.
+ *  - orc_solver_evaluate_viscosity: the law on the current fields without relaxation into mu, the strain-rate magnitude it was
+ *    evaluated at into strain_rate (may be NULL); changes no bit of the solver.  Needs the arm on.
+ *  - orc_solver_get_diffusion: a_di in the CSR order of orc_mesh_matrix_pattern and the three wall terms (each may be NULL).
+ *  - orc_solver_surface_report and orc_solver_boundary_fields use the cell's viscosity in d = (mu A) / dist and in y+ while the arm
+ *    is on; orc_surface_integrals and orc_boundary_fields keep the constant they are given.
+ *  - orc_solver_snapshot / orc_solver_restore include the viscosity field and the first-evaluation flag while the arm is on.
+ *  - On a partitioned mesh every rank makes the same calls in the same order: the set calls, orc_solver_evaluate_viscosity and
+ *    orc_solver_assemble_momentum exchange ghost values (the velocities', then the viscosity's) while the arm is on.
+ * Refused with ORC_ERR_BAD_ARGUMENT and the solver unchanged: a parameter outside its range or not finite, an unknown model or face
+ * interpolation, FIELD without a field, a field entry that is not positive and finite, and a solver with frozen_diagonals = 0. */
+void orc_viscosity_default(OrcViscosity *c);
+int orc_solver_set_viscosity(OrcSolver *s, const OrcViscosity *c);
+int orc_solver_set_viscosity_field(OrcSolver *s, const double *mu /*[n_cells]*/);
+int orc_solver_get_viscosity(OrcSolver *s, double *mu /*[n_cells]*/);
+int orc_solver_evaluate_viscosity(OrcSolver *s, double *mu /*[n_cells]*/, double *strain_rate /*[n_cells], may be NULL*/);
+int orc_solver_get_diffusion(OrcSolver *s, double *a_di /*[nnz]*/, double *b_u_di, double *b_v_di, double *b_w_di /*[n_cells] each*/);
+/* the two passes of the arm on the solver's current state, HIP-event average ms per launch over `reps`: avg_ms[0] the law pass
+ * (viscosity_cell_k, into scratch), avg_ms[1] the rebuild (diffusion_var_k); needs the arm on, changes no bit of the solver */
+int orc_bench_viscosity(OrcSolver *s, int reps, double avg_ms[2]);
 
 /* ---------- measurement hooks (bench.py): HIP-event timed launches of single kernels ---------- */
 /* y = A x with the momentum matrix a_u of the solver, `reps` launches; returns average ms per launch */

@@ -280,6 +280,31 @@ typedef struct OrcConvergence {
     int32_t reserved0;            /* 0 */
 } OrcConvergence;
 
+/* Variable viscosity (new-build extension; orc_amd.h: orc_solver_set_viscosity): a per-cell viscosity in the momentum diffusion, either
+ * prescribed (FIELD) or a law of the strain-rate magnitude g = ORC_DERIVED_STRAIN_RATE_MAG of the settings' gradient scheme, bit for bit.
+ * DESIGN.md §3 "Variable viscosity" fixes the operator order. */
+enum OrcViscosityModel {
+    ORC_VISCOSITY_FIELD = 1,       /* the data of orc_solver_set_viscosity_field, neither clamped nor relaxed */
+    ORC_VISCOSITY_POWER_LAW = 2,   /* m = k * pow(g, n - 1) */
+    ORC_VISCOSITY_CARREAU = 3,     /* t = lambda * g; m = mu_inf + (mu_zero - mu_inf) * pow(1 + t * t, (n - 1) / 2) */
+    ORC_VISCOSITY_SMAGORINSKY = 4  /* l = cs * cbrt(V_P); m = mu + (rho * (l * l)) * g, mu and rho the solver's */
+};
+/* the viscosity of an interior face from its two cells, lo = fmin(mu_P, mu_N), hi = fmax(mu_P, mu_N); a boundary face takes mu_P */
+enum OrcViscosityFace {
+    ORC_VISCOSITY_FACE_ARITHMETIC = 0, /* (lo + hi) * 0.5 */
+    ORC_VISCOSITY_FACE_HARMONIC = 1    /* lo * (hi / ((lo + hi) * 0.5)) */
+};
+typedef struct OrcViscosity {
+    int32_t model;              /* OrcViscosityModel */
+    int32_t face_interpolation; /* OrcViscosityFace */
+    double k, n;                /* POWER_LAW: k > 0, n finite; CARREAU also uses n */
+    double mu_zero, mu_inf;     /* CARREAU: >= 0 */
+    double lambda;              /* CARREAU: >= 0 */
+    double cs;                  /* SMAGORINSKY: >= 0 */
+    double mu_min, mu_max;      /* every law (not FIELD): mu = fmin(fmax(m, mu_min), mu_max); 0 < mu_min <= mu_max < inf */
+    double relaxation;          /* (0, 1]: the stored field becomes mu_old + w (mu - mu_old); 1 = none, no arithmetic */
+} OrcViscosity;
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,23 @@ def lib():
             L.orc_solve_steady_converged.restype = C.c_int
             L.orc_solver_get_pressure_rhs.argtypes = [C.c_void_p, _f64]
             L.orc_solver_get_pressure_rhs.restype = C.c_int
+        # variable viscosity (orc_amd.h "variable viscosity"): full signatures
+        if hasattr(L, "orc_solver_set_viscosity"):
+            _f64 = C.POINTER(C.c_double)
+            L.orc_viscosity_default.argtypes = [C.c_void_p]
+            L.orc_viscosity_default.restype = None
+            L.orc_solver_set_viscosity.argtypes = [C.c_void_p, C.c_void_p]
+            L.orc_solver_set_viscosity.restype = C.c_int
+            L.orc_solver_set_viscosity_field.argtypes = [C.c_void_p, _f64]
+            L.orc_solver_set_viscosity_field.restype = C.c_int
+            L.orc_solver_get_viscosity.argtypes = [C.c_void_p, _f64]
+            L.orc_solver_get_viscosity.restype = C.c_int
+            L.orc_solver_evaluate_viscosity.argtypes = [C.c_void_p, _f64, _f64]
+            L.orc_solver_evaluate_viscosity.restype = C.c_int
+            L.orc_solver_get_diffusion.argtypes = [C.c_void_p, _f64, _f64, _f64, _f64]
+            L.orc_solver_get_diffusion.restype = C.c_int
+            L.orc_bench_viscosity.argtypes = [C.c_void_p, C.c_int, _f64]
+            L.orc_bench_viscosity.restype = C.c_int
         # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
         if hasattr(L, "orc_debug_amg_setup_stats"):
             L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]

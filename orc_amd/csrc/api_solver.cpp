@@ -341,6 +341,12 @@ int orc_solver_snapshot(OrcSolver *s) {
         }
         t.sc.snap_levels = t.sc.levels;
     }
+    t.vis.snap_on = t.vis.on;
+    if (t.vis.on) {  // the viscosity field and whether its next evaluation is the first (orc_solver_set_viscosity)
+        ORC_TRY(t.vis.snap_mu.ensure((size_t)std::max<int64_t>(t.n, 1)));
+        ORC_TRY(vec_copy(t.vis.snap_mu.p, t.vis.mu.p, t.n));
+        t.vis.snap_first = t.vis.first;
+    }
     t.snap_iterations = t.iterations_done;
     t.has_snapshot = true;
     return ORC_OK;
@@ -362,6 +368,10 @@ int orc_solver_restore(OrcSolver *s) {
         for (int k = 0; k < 2; ++k) ORC_TRY(vec_copy(t.sc.lev[k].p, t.sc.snap_lev[k].p, t.n));
         t.sc.levels = t.sc.snap_levels;
     }
+    if (t.vis.snap_on && t.vis.on) {
+        ORC_TRY(vec_copy(t.vis.mu.p, t.vis.snap_mu.p, t.n));
+        t.vis.first = t.vis.snap_first;
+    }
     t.iterations_done = t.snap_iterations;
     return ORC_OK;
 }
@@ -371,6 +381,10 @@ int orc_solver_assemble_momentum(OrcSolver *s, double *a_u, double *a_v, double 
     if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
     SolverState &t = s->st;
     const bool tvd = t.settings.momentum >= ORC_MOMENTUM_TVD_LUD;
+    if (t.vis.on) {  // variable viscosity: as an iteration does it, behind the exchange of the fields' ghosts
+        ORC_TRY(exchange_fields(t));
+        ORC_TRY(k_viscosity_update(t));
+    }
     ORC_TRY(k_gradients(t, tvd));
     ORC_TRY(k_face_flux(t, true));
     double pe[3];

@@ -210,6 +210,19 @@ struct SolverState {
         int snap_levels = 0;
         bool snap_on = false;
     } sc;
+    // Variable viscosity (orc_solver_set_viscosity, viscosity.hip): off unless enabled, every buffer allocated by a set call.  While it
+    // is on, a_di and b_*_di are rebuilt from `mu` ahead of every momentum assembly; off again, they are k_diffusion's.
+    struct Viscosity {
+        bool on = false;
+        OrcViscosity c{};
+        DevBuf<double> mu;      // [n] the field the last assembly used (ghost entries exchanged before the rebuild)
+        DevBuf<double> field;   // [n] the FIELD model's data as set
+        bool has_field = false;
+        bool first = true;      // the next evaluation of an assembly takes the law's value itself (no relaxation)
+        DevBuf<double> snap_mu;
+        bool snap_on = false, snap_first = true;
+    } vis;
+    const double *cell_viscosity() const { return vis.on ? vis.mu.p : nullptr; }  // what the surface reports and boundary maps take
 };
 
 int mesh_upload(OrcMesh &m, int64_t n_own, int64_t n_cells, int64_t n_faces, int32_t n_zones, const int64_t *face_c0, const int64_t *face_c1,
@@ -271,8 +284,9 @@ int solve_scalar_system(SolverState &s, const OrcSettings &t);
 // one scalar solve of orc_solver_advance (levels shifted first), the report kept in s.sc.report
 int scalar_step_dev(SolverState &s);
 // surface reports (surface.hip): per zone ORC_SURFACE_N sums of the device fields u, v, w, p (the mesh's internal cell order) to the host
+// mu_cell (may be null): a per-cell viscosity of the same order that replaces mu in the viscous terms
 int surface_report_dev(OrcMesh &m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
-                       const double origin[3], double *per_zone);
+                       const double *mu_cell, const double origin[3], double *per_zone);
 // the boundary index of the mesh (m.surface), built at first use: what the reports and the boundary maps of derived.hip walk
 int surface_index(OrcMesh &m);
 // residual monitors (residuals.hip), all asynchronous on ctx().stream: the fused pass over a_u/a_v/a_w, b_u/b_v/b_w and the fields they
@@ -284,6 +298,13 @@ int k_momentum_residuals(SolverState &s);
 int k_imbalance(SolverState &s);
 int monitor_fetch(SolverState &s);
 void monitor_append(SolverState &s);
+// variable viscosity (viscosity.hip), asynchronous on ctx().stream.  k_viscosity: viscosity_cell_k, the law on the current fields into
+// mu_out (relaxed against mu_out's old content when `relax`), the strain-rate magnitude into g_out (may be null).  k_diffusion_var:
+// diffusion_var_k, a_di and b_*_di from s.vis.mu.  k_viscosity_update: what an assembly runs ahead of k_face_flux while the arm is on
+// (the fields' ghosts are current): the law (not FIELD), one exchange of the viscosity's ghosts, the rebuild.
+int k_viscosity(SolverState &s, double *mu_out, double *g_out, bool relax);
+int k_diffusion_var(SolverState &s);
+int k_viscosity_update(SolverState &s);
 
 }  // namespace orc
 

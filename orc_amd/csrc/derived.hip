@@ -39,9 +39,8 @@ __device__ __forceinline__ void derived_store(const DerivedArgs &A, int64_t n, i
     if (mask & (1u << ORC_DERIVED_VORTICITY_Z)) { *o = wz; o += n; }
     if (mask & (1u << ORC_DERIVED_VORTICITY_MAG)) { *o = sqrt((wx * wx + wy * wy) + wz * wz); o += n; }
     if (mask & ((1u << ORC_DERIVED_STRAIN_RATE_MAG) | (1u << ORC_DERIVED_Q_CRITERION))) {
-        const double s01 = (gx.y + gy.x) / 2., s02 = (gx.z + gz.x) / 2., s12 = (gy.z + gz.y) / 2.;
-        const double ss = ((gx.x * gx.x + gy.y * gy.y) + gz.z * gz.z) + 2. * ((s01 * s01 + s02 * s02) + s12 * s12);
-        if (mask & (1u << ORC_DERIVED_STRAIN_RATE_MAG)) { *o = sqrt(2. * ss); o += n; }
+        const double ss = strain_ss(gx, gy, gz);  // gradient_cell.hpp: shared with the viscosity laws
+        if (mask & (1u << ORC_DERIVED_STRAIN_RATE_MAG)) { *o = strain_rate_mag(ss); o += n; }
         if (mask & (1u << ORC_DERIVED_Q_CRITERION)) {
             const double w01 = (gx.y - gy.x) / 2., w02 = (gx.z - gz.x) / 2., w12 = (gy.z - gz.y) / 2.;
             const double oo = 2. * ((w01 * w01 + w02 * w02) + w12 * w12);
@@ -88,6 +87,7 @@ struct BoundaryArgs {
     int64_t nb;
     const double *u, *v, *w, *p;
     double rho, mu;
+    const double *mu_cell;  // null, or the per-cell viscosity that replaces mu (variable viscosity on: the face's cell)
     double *out;  // [popcount(mask)][nb]
     uint32_t mask;
 };
@@ -121,12 +121,13 @@ __global__ __launch_bounds__(kBlock) void boundary_map_k(MeshDev M, BoundaryArgs
             if (vec_bc) {
                 const double dx = M.fcx[f] - M.ccx[P], dy = M.fcy[f] - M.ccy[P], dz = M.fcz[f] - M.ccz[P];
                 const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
-                const double d = (A.mu * a) / dist;
+                const double mu = A.mu_cell ? A.mu_cell[P] : A.mu;
+                const double d = (mu * a) / dist;
                 tx = (d * (upx - ufx)) / a; ty = (d * (upy - ufy)) / a; tz = (d * (upz - ufz)) / a;
                 const double tn = (tx * nx + ty * ny) + tz * nz;
                 const double sx = tx - tn * nx, sy = ty - tn * ny, sz = tz - tn * nz;
                 shear = sqrt((sx * sx + sy * sy) + sz * sz);
-                yplus = ((A.rho * sqrt(shear / A.rho)) * dist) / A.mu;
+                yplus = ((A.rho * sqrt(shear / A.rho)) * dist) / mu;
             }
         }
         const double val[ORC_BOUNDARY_N] = {pf, tx, ty, tz, shear, yplus, flux, a};
@@ -184,8 +185,8 @@ int derived_fields_dev(OrcMesh &m, double *u, double *v, double *w, const OrcSet
     return fetch(status, m.halo.active(), "derived fields");
 }
 
-int boundary_fields_dev(OrcMesh &m, const double *u, const double *v, const double *w, const double *p, double rho, double mu, uint32_t mask,
-                        double *out) {
+int boundary_fields_dev(OrcMesh &m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
+                        const double *mu_cell, uint32_t mask, double *out) {
     ORC_TRY(surface_index(m));
     const SurfaceIndex &X = *m.surface;
     const int k = popcount32(mask);
@@ -196,7 +197,7 @@ int boundary_fields_dev(OrcMesh &m, const double *u, const double *v, const doub
     if (nb > 0) {
         DevBuf<double> dev;
         ORC_TRY(dev.alloc((size_t)k * (size_t)nb));
-        BoundaryArgs A{X.bface.p, nb, u, v, w, p, rho, mu, dev.p, mask};
+        BoundaryArgs A{X.bface.p, nb, u, v, w, p, rho, mu, mu_cell, dev.p, mask};
         hipLaunchKernelGGL(boundary_map_k, dim3(grid_for(nb)), dim3(kBlock), 0, ctx().stream, m.dev(), A, status.p);
         ORC_HIP(hipGetLastError());
         ORC_TRY(dev.download(out, (size_t)k * (size_t)nb));
@@ -244,7 +245,7 @@ int orc_solver_boundary_fields(OrcSolver *s, uint32_t mask, double *out) {
     if (!s || !out) return set_error(ORC_ERR_BAD_ARGUMENT, "boundary fields: null argument");
     if (mask == 0 || (mask >> ORC_BOUNDARY_N) != 0) return set_error(ORC_ERR_BAD_ARGUMENT, "boundary fields: mask 0x%x selects nothing or an unknown field", mask);
     SolverState &st = s->st;
-    return boundary_fields_dev(*st.mesh, st.u.p, st.v.p, st.w.p, st.p.p, st.rho, st.mu, mask, out);
+    return boundary_fields_dev(*st.mesh, st.u.p, st.v.p, st.w.p, st.p.p, st.rho, st.mu, st.cell_viscosity(), mask, out);
 }
 
 int orc_boundary_fields(OrcMesh *m, const double *u, const double *v, const double *w, const double *p, double rho, double mu, uint32_t mask,
@@ -257,7 +258,7 @@ int orc_boundary_fields(OrcMesh *m, const double *u, const double *v, const doub
     const double *src[4] = {u, v, w, p};
     DevBuf<double> dev[4];
     for (int k = 0; k < 4; ++k) ORC_TRY(upload_in_internal_order(*m, src[k], dev[k]));
-    return boundary_fields_dev(*m, dev[0].p, dev[1].p, dev[2].p, dev[3].p, rho, mu, mask, out);
+    return boundary_fields_dev(*m, dev[0].p, dev[1].p, dev[2].p, dev[3].p, rho, mu, nullptr, mask, out);
 }
 
 }  // extern "C"

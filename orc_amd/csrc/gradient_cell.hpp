@@ -1,6 +1,7 @@
 // gradient_cell.hpp — the per-cell velocity-gradient arithmetic of the assembly (K9), shared by grad_u_k / grad_u_lsq_k
-// (assembly.hip) and derived_cell_k (derived.hip): the small vector type, the boundary-value rules and the two per-cell bodies;
-// the grid-stride loop of the assembly kernels (assembly.hip, initialize.hip).
+// (assembly.hip), derived_cell_k (derived.hip) and viscosity_cell_k (viscosity.hip): the small vector type, the boundary-value rules, the
+// two per-cell bodies and the strain-rate magnitude the last two form from them; the grid-stride loop of the assembly kernels
+// (assembly.hip, initialize.hip).
 // Device code only.  Every operation and its order are the reference's; a kernel that calls a body gets the same bits as any other.
 #pragma once
 #include "assembly.hpp"
@@ -175,6 +176,15 @@ __device__ __forceinline__ void grad_u_lsq_cell(const MeshDev &M, const double *
         inv_times3(L.ata, L.atb[2], g[2]);
     }
 }
+
+// SS = S : S of the gradient rows gx, gy, gz (G[i][j] = row i, component j) and the strain-rate magnitude sqrt(2 SS), in THE operator
+// order of DESIGN §3 "Derived fields and boundary maps": what derived_store (derived.hip) writes as ORC_DERIVED_STRAIN_RATE_MAG and
+// what viscosity_cell_k (viscosity.hip) evaluates its law at — one expression, the same bits.
+__device__ __forceinline__ double strain_ss(V3 gx, V3 gy, V3 gz) {
+    const double s01 = (gx.y + gy.x) / 2., s02 = (gx.z + gz.x) / 2., s12 = (gy.z + gz.y) / 2.;
+    return ((gx.x * gx.x + gy.y * gy.y) + gz.z * gz.z) + 2. * ((s01 * s01 + s02 * s02) + s12 * s12);
+}
+__device__ __forceinline__ double strain_rate_mag(double ss) { return sqrt(2. * ss); }
 
 }  // namespace orc
 #endif

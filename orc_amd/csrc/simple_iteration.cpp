@@ -418,6 +418,7 @@ int solver_iterate(SolverState &s, uint64_t iterations, double *report) {
         if (s.arena.empty()) ORC_TRY(s.arena.reset());  // between iterations nothing in the solver's own arena is alive
         ORC_TRACE("iteration %llu: start", (unsigned long long)s.iterations_done);
         ORC_TRY(exchange_fields(s));
+        if (s.vis.on) ORC_TRY(k_viscosity_update(s));            // variable viscosity: the law on the fresh fields, then a_di and b_*_di
         ORC_TRY(k_gradients(s, tvd));
         ORC_TRY(exchange_gradient(s, s.gp.p));
         ORC_TRY(k_face_flux(s, true));

@@ -90,6 +90,7 @@ struct SurfaceArgs {
     const int4 *chunk;  // {zone, begin, end, 0}
     const double *u, *v, *w, *p;
     double rho, mu, x0, y0, z0;
+    const double *mu_cell;  // null, or the per-cell viscosity that replaces mu (variable viscosity on: the face's cell)
 };
 
 // what a zone type means for a boundary face (get_face_velocity solver.rs:952-1003, get_face_pressure :1104-1150, get_face_flux
@@ -118,7 +119,7 @@ __device__ __forceinline__ void surface_terms(const MeshDev &M, const SurfaceArg
     double fvx = 0., fvy = 0., fvz = 0.;
     if (R.vec_bc) {
         const double dx = fx - M.ccx[P], dy = fy - M.ccy[P], dz = fz - M.ccz[P];
-        const double d = (A.mu * a) / sqrt((dx * dx + dy * dy) + dz * dz);
+        const double d = ((A.mu_cell ? A.mu_cell[P] : A.mu) * a) / sqrt((dx * dx + dy * dy) + dz * dz);
         fvx = d * (upx - ufx); fvy = d * (upy - ufy); fvz = d * (upz - ufz);
     }
     const double rx = fx - A.x0, ry = fy - A.y0, rz = fz - A.z0;
@@ -278,14 +279,14 @@ bool finite3(const double *x) { return std::isfinite(x[0]) && std::isfinite(x[1]
 int surface_index(OrcMesh &m) { return ensure_index(m); }
 
 int surface_report_dev(OrcMesh &m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
-                       const double origin[3], double *per_zone) {
+                       const double *mu_cell, const double origin[3], double *per_zone) {
     ORC_TRY(ensure_index(m));
     SurfaceIndex &X = *m.surface;
     const int Z = m.n_zones;
     SurfaceArgs A{};
     A.bface = X.bface.p; A.chunk = reinterpret_cast<const int4 *>(X.chunk.p);
     A.u = u; A.v = v; A.w = w; A.p = p;
-    A.rho = rho; A.mu = mu;
+    A.rho = rho; A.mu = mu; A.mu_cell = mu_cell;
     A.x0 = origin ? origin[0] : 0.; A.y0 = origin ? origin[1] : 0.; A.z0 = origin ? origin[2] : 0.;
     ORC_TRY(X.status.zero());
     if (X.n_chunks > 0) hipLaunchKernelGGL(surface_zone_k, dim3((unsigned)X.n_chunks), dim3(kBlock), 0, ctx().stream, m.dev(), A, X.partials.p, X.status.p);
@@ -313,7 +314,7 @@ int orc_solver_surface_report(OrcSolver *s, const double origin[3], double *per_
     if (!s || !per_zone) return set_error(ORC_ERR_BAD_ARGUMENT, "surface report: null argument");
     if (origin && !finite3(origin)) return set_error(ORC_ERR_BAD_ARGUMENT, "surface report: the origin must be finite");
     SolverState &st = s->st;
-    return surface_report_dev(*st.mesh, st.u.p, st.v.p, st.w.p, st.p.p, st.rho, st.mu, origin, per_zone);
+    return surface_report_dev(*st.mesh, st.u.p, st.v.p, st.w.p, st.p.p, st.rho, st.mu, st.cell_viscosity(), origin, per_zone);
 }
 
 int orc_surface_integrals(OrcMesh *m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
@@ -334,7 +335,7 @@ int orc_surface_integrals(OrcMesh *m, const double *u, const double *v, const do
         for (size_t c = 0; c < n; ++c) tmp[c] = src[k][g[c]];
         ORC_TRY(dev[k].upload(tmp.data(), n));
     }
-    return surface_report_dev(*m, dev[0].p, dev[1].p, dev[2].p, dev[3].p, rho, mu, origin, per_zone);
+    return surface_report_dev(*m, dev[0].p, dev[1].p, dev[2].p, dev[3].p, rho, mu, nullptr, origin, per_zone);
 }
 
 int orc_mesh_boundary_index(OrcMesh *m, int64_t *zone_ptr, int32_t *faces, int64_t *n_builds, int32_t *chunk) {

@@ -1,0 +1,396 @@
+// viscosity.hip — variable viscosity (new-build extension; ORC knows one constant mu): a per-cell viscosity field, prescribed or a law
+// of the strain-rate magnitude, and the diffusion matrix rebuilt from it.  DESIGN.md §3 "Variable viscosity" has the definitions and
+// the operator order; orc_types.h OrcViscosity names the parameters.
+//
+//   viscosity_cell_k   one thread per owned cell, derived_cell_k's XCD-contiguous block walk: the velocity gradient of the settings'
+//                      reconstruction by the assembly's own per-cell body (gradient_cell.hpp), g = strain_rate_mag(strain_ss(G)) — the
+//                      bits of ORC_DERIVED_STRAIN_RATE_MAG — then the law, the clamp and the relaxation; writes mu and, for
+//                      orc_solver_evaluate_viscosity, g.  Model and relaxation are wave-uniform arguments.
+//   diffusion_var_k    one thread per owned row, the same walk: diffusion_k's loop (assembly.hip) with mu replaced by the face
+//                      viscosity, i.e. one more gather (mu_N) per interior face; writes a_di, b_u_di, b_v_di, b_w_di
+// momentum_k reads the diffusion coefficients from a_di and the wall terms from b_*_di and never sees mu: neither it, nor the Rhie-Chow
+// path, nor any solve changes.  Opt-in: neither kernel is launched unless orc_solver_set_viscosity has switched the arm on.  Both are
+// gather-bound like the kernels they are modelled on; no atomics but the status word, no LDS.
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <initializer_list>
+
+#include "assembly.hpp"
+#include "gradient_cell.hpp"
+
+namespace orc {
+
+namespace {
+
+// Blocks of kBlock cells; XCD g (workgroups g, g + 8, ...) walks a contiguous eighth of the blocks, so that the two cells of a face
+// mostly share one L2 (momentum_k, scalar_k, derived_cell_k).  A grid that is no multiple of 8 strides plainly.
+struct BlockWalk {
+    int vb, vb_end, vb_step;
+};
+__device__ __forceinline__ BlockWalk block_walk(int n_items) {
+    const int n_blk = (n_items + kBlock - 1) / kBlock;
+    BlockWalk w{(int)blockIdx.x, n_blk, (int)gridDim.x};
+    if ((gridDim.x & 7) == 0 && gridDim.x >= 8) {
+        const int per = (n_blk + 7) / 8;
+        const int xcd = blockIdx.x & 7;
+        w.vb = xcd * per + (int)(blockIdx.x >> 3);
+        w.vb_end = (xcd + 1) * per < n_blk ? (xcd + 1) * per : n_blk;
+        w.vb_step = gridDim.x >> 3;
+    }
+    return w;
+}
+
+struct ViscosityArgs {
+    const double *u, *v, *w;
+    const double *field;  // FIELD: the prescribed viscosity
+    double *mu;           // [n_cells] out; with relax also the old field
+    double *g;            // [n_cells] out, may be null
+    int model, relax;     // the same in every lane
+    double k, n, mu_zero, mu_inf, lambda, cs, mu_min, mu_max, relaxation;
+    double rho, mu_lam;   // the solver's density and (laminar) viscosity: SMAGORINSKY
+};
+
+// The law at strain-rate magnitude g in a cell of volume vol, then the clamp: THE operator order of DESIGN §3 "Variable viscosity".
+// g = 0 with n < 1 makes pow return +inf, which the clamp turns into mu_max: intended.
+__device__ __forceinline__ double viscosity_law(const ViscosityArgs &A, double g, double vol) {
+    double m;
+    if (A.model == ORC_VISCOSITY_POWER_LAW) {
+        m = A.k * pow(g, A.n - 1.);
+    } else if (A.model == ORC_VISCOSITY_CARREAU) {
+        const double t = A.lambda * g;
+        m = A.mu_inf + (A.mu_zero - A.mu_inf) * pow(1. + t * t, (A.n - 1.) / 2.);
+    } else {  // SMAGORINSKY
+        const double l = A.cs * cbrt(vol);
+        m = A.mu_lam + (A.rho * (l * l)) * g;
+    }
+    return fmin(fmax(m, A.mu_min), A.mu_max);
+}
+
+// Reads what grad_u_k / grad_u_lsq_k read; writes one double per cell (two for orc_solver_evaluate_viscosity).
+template <bool kLsq>
+__global__ __launch_bounds__(kBlock) void viscosity_cell_k(MeshDev M, ViscosityArgs A, int *status) {
+    const int n_items = (int)M.n_own;  // cell ids are int32 (MeshDev.c0)
+    for (BlockWalk W = block_walk(n_items); W.vb < W.vb_end; W.vb += W.vb_step) {
+        const int c = W.vb * kBlock + (int)threadIdx.x;
+        if (c >= n_items) break;
+        V3 gx, gy, gz;
+        double conv;
+        if (kLsq) {
+            double g[3][3];
+            grad_u_lsq_cell<false>(M, A.u, A.v, A.w, c, status, g, conv);
+            gx = mk(g[0][0], g[0][1], g[0][2]); gy = mk(g[1][0], g[1][1], g[1][2]); gz = mk(g[2][0], g[2][1], g[2][2]);
+        } else {
+            grad_u_gg_cell<false>(M, A.u, A.v, A.w, c, status, gx, gy, gz, conv);
+        }
+        const double g = strain_rate_mag(strain_ss(gx, gy, gz));
+        if (A.g) A.g[c] = g;
+        double mu;
+        if (A.model == ORC_VISCOSITY_FIELD) {
+            mu = A.field[c];
+        } else {
+            mu = viscosity_law(A, g, M.vol[c]);
+            if (A.relax) {
+                const double old = A.mu[c];
+                mu = old + A.relaxation * (mu - old);
+            }
+        }
+        A.mu[c] = mu;
+    }
+}
+
+// symmetric in its two cells, and exactly mu where both hold mu: (mu + mu) * 0.5 = mu, mu / mu = 1, mu * 1 = mu
+__device__ __forceinline__ double face_viscosity(int harmonic, double mu_p, double mu_n) {
+    const double lo = fmin(mu_p, mu_n), hi = fmax(mu_p, mu_n);
+    const double mean = (lo + hi) * 0.5;
+    return harmonic ? lo * (hi / mean) : mean;
+}
+
+// diffusion_k (assembly.hip; discretization.rs:39-131) with mu replaced by the face viscosity: the same branches per zone type, the
+// same accumulation order of a_p and of the wall terms, d_i = mu_f * A / dist.  A boundary face takes its cell's viscosity.
+__global__ __launch_bounds__(kBlock) void diffusion_var_k(MeshDev M, SellDev P, const double *__restrict__ mu, int harmonic,
+                                                          double *__restrict__ a_di, double *__restrict__ b_u, double *__restrict__ b_v,
+                                                          double *__restrict__ b_w, int *status) {
+    const int n_items = (int)M.n_own;
+    for (BlockWalk W = block_walk(n_items); W.vb < W.vb_end; W.vb += W.vb_step) {
+        const int c = W.vb * kBlock + (int)threadIdx.x;
+        if (c >= n_items) break;
+        const V3 cc = cell_centroid(M, c);
+        const double mu_p = mu[c];
+        double a_p = 0., bu = 0., bv = 0., bw = 0.;
+        for (int q = M.cfp[c]; q < M.cfp[c + 1]; ++q) {
+            const int f = M.cf[q];
+            const int z = M.fzone[f];
+            const int zt = M.ztype[z];
+            double d_i = 0.;
+            if (zt == ORC_BC_WALL || zt == ORC_BC_VELOCITY_INLET) {
+                d_i = mu_p * M.area[f] / vnorm(vsub(face_centroid(M, f), cc));
+                const V3 sc = vmuls(zone_vec(M, z), d_i);
+                bu += sc.x; bv += sc.y; bw += sc.z;
+            } else if (zt == ORC_BC_PRESSURE_INLET || zt == ORC_BC_PRESSURE_OUTLET || zt == ORC_BC_SYMMETRY) {
+                d_i = 0.;
+            } else if (zt == ORC_BC_INTERIOR) {
+                const int nb = (M.c0[f] == c) ? M.c1[f] : M.c0[f];
+                d_i = face_viscosity(harmonic, mu_p, mu[nb]) * M.area[f] / vnorm(vsub(cell_centroid(M, nb), cc));
+                a_di[M.cfpos[q]] = -d_i;
+            } else {
+                raise(status, ORC_ERR_UNSUPPORTED_BC);
+            }
+            a_p += d_i;
+        }
+        a_di[P.diag_pos[c]] = a_p;
+        b_u[c] = bu; b_v[c] = bv; b_w[c] = bw;
+    }
+}
+
+bool finite_all(std::initializer_list<double> xs) {
+    for (double x : xs)
+        if (!std::isfinite(x)) return false;
+    return true;
+}
+
+int validate(const OrcViscosity &c) {
+    if (c.model < ORC_VISCOSITY_FIELD || c.model > ORC_VISCOSITY_SMAGORINSKY) return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: unknown model %d", c.model);
+    if (c.face_interpolation != ORC_VISCOSITY_FACE_ARITHMETIC && c.face_interpolation != ORC_VISCOSITY_FACE_HARMONIC)
+        return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: unknown face interpolation %d", c.face_interpolation);
+    if (!finite_all({c.k, c.n, c.mu_zero, c.mu_inf, c.lambda, c.cs, c.mu_min, c.mu_max, c.relaxation}))
+        return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: every parameter must be finite");
+    if (!(c.cs >= 0.)) return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: cs must be >= 0");
+    if (!(c.mu_min > 0.) || !(c.mu_min <= c.mu_max)) return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: the clamp needs 0 < mu_min <= mu_max < inf");
+    if (!(c.relaxation > 0.) || !(c.relaxation <= 1.)) return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: relaxation must lie in (0, 1]");
+    if (c.model == ORC_VISCOSITY_POWER_LAW && !(c.k > 0.)) return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: the power law needs k > 0");
+    if (c.model == ORC_VISCOSITY_CARREAU && (!(c.mu_zero >= 0.) || !(c.mu_inf >= 0.) || !(c.lambda >= 0.)))
+        return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: Carreau needs mu_zero, mu_inf and lambda >= 0");
+    return ORC_OK;
+}
+
+int exchange_velocities(SolverState &s) {
+    if (!s.mesh->halo.active()) return ORC_OK;
+    double *f[3] = {s.u.p, s.v.p, s.w.p};
+    return s.mesh->halo.exchange(f, 3);
+}
+
+// the viscosity's ghosts, then a_di and b_*_di from it
+int exchange_and_rebuild(SolverState &s) {
+    if (s.mesh->halo.active()) ORC_TRY(s.mesh->halo.exchange(s.vis.mu.p));
+    return k_diffusion_var(s);
+}
+
+int status_of(SolverState &s, const char *what) {
+    int h = fetch_status(s);
+    if (s.mesh->halo.active()) h = comm_global_status(h);
+    if (h == ORC_ERR_SINGULAR_MATRIX) return set_error(h, "%s: singular least-squares system", what);
+    if (h != ORC_OK) return set_error(h, "%s: a boundary face lies in a zone whose type the assembly does not support", what);
+    return ORC_OK;
+}
+
+int download_orc_order(const SolverState &s, const double *dev, double *dst) {
+    const size_t n = (size_t)s.n;
+    const std::vector<int64_t> &g = s.mesh->h_global_ids;  // reordered mesh: internal cell c holds ORC cell g[c]
+    std::vector<double> tmp;
+    double *host = g.empty() ? dst : (tmp.resize(n), tmp.data());
+    if (n) ORC_HIP(hipMemcpyAsync(host, dev, n * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
+    ORC_HIP(hipStreamSynchronize(ctx().stream));
+    if (!g.empty())
+        for (size_t c = 0; c < n; ++c) dst[g[c]] = tmp[c];
+    return ORC_OK;
+}
+
+}  // namespace
+
+int k_viscosity(SolverState &s, double *mu_out, double *g_out, bool relax) {
+    OrcMesh &m = *s.mesh;
+    const OrcViscosity &c = s.vis.c;
+    ViscosityArgs A{};
+    A.u = s.u.p; A.v = s.v.p; A.w = s.w.p;
+    A.field = s.vis.field.p;
+    A.mu = mu_out; A.g = g_out;
+    A.model = c.model;
+    A.relax = relax ? 1 : 0;
+    A.k = c.k; A.n = c.n; A.mu_zero = c.mu_zero; A.mu_inf = c.mu_inf; A.lambda = c.lambda; A.cs = c.cs;
+    A.mu_min = c.mu_min; A.mu_max = c.mu_max; A.relaxation = c.relaxation;
+    A.rho = s.rho; A.mu_lam = s.mu;
+    const int g = grid_for(s.n_own);
+    if (s.settings.gradient_reconstruction == ORC_GRAD_LEAST_SQUARES)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(viscosity_cell_k<true>), dim3(g), dim3(kBlock), 0, ctx().stream, m.dev(), A, s.dev_status.p);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(viscosity_cell_k<false>), dim3(g), dim3(kBlock), 0, ctx().stream, m.dev(), A, s.dev_status.p);
+    ORC_HIP(hipGetLastError());
+    return ORC_OK;
+}
+
+int k_diffusion_var(SolverState &s) {
+    OrcMesh &m = *s.mesh;
+    hipLaunchKernelGGL(diffusion_var_k, dim3(grid_for(s.n_own)), dim3(kBlock), 0, ctx().stream, m.dev(), m.pat.dev(), s.vis.mu.p,
+                       s.vis.c.face_interpolation == ORC_VISCOSITY_FACE_HARMONIC ? 1 : 0, s.a_di.p, s.b_u_di.p, s.b_v_di.p, s.b_w_di.p,
+                       s.dev_status.p);
+    ORC_HIP(hipGetLastError());
+    return ORC_OK;
+}
+
+int k_viscosity_update(SolverState &s) {
+    SolverState::Viscosity &V = s.vis;
+    if (V.c.model != ORC_VISCOSITY_FIELD) {
+        ORC_TRY(k_viscosity(s, V.mu.p, nullptr, !V.first && V.c.relaxation < 1.));
+        V.first = false;
+    }
+    return exchange_and_rebuild(s);
+}
+
+}  // namespace orc
+
+using namespace orc;
+
+extern "C" {
+
+static_assert(sizeof(OrcViscosity) == 80 && offsetof(OrcViscosity, model) == 0 && offsetof(OrcViscosity, face_interpolation) == 4 &&
+                  offsetof(OrcViscosity, k) == 8 && offsetof(OrcViscosity, n) == 16 && offsetof(OrcViscosity, mu_zero) == 24 &&
+                  offsetof(OrcViscosity, mu_inf) == 32 && offsetof(OrcViscosity, lambda) == 40 && offsetof(OrcViscosity, cs) == 48 &&
+                  offsetof(OrcViscosity, mu_min) == 56 && offsetof(OrcViscosity, mu_max) == 64 && offsetof(OrcViscosity, relaxation) == 72,
+              "OrcViscosity is part of the ABI (orc_amd/settings.py Viscosity mirrors it)");
+
+void orc_viscosity_default(OrcViscosity *c) {
+    if (!c) return;
+    *c = OrcViscosity{};
+    c->model = ORC_VISCOSITY_POWER_LAW;  // with n = 1: Newtonian, mu = k
+    c->face_interpolation = ORC_VISCOSITY_FACE_ARITHMETIC;
+    c->k = 1e-3; c->n = 1.;
+    c->mu_zero = 1e-3; c->mu_inf = 0.; c->lambda = 1.;
+    c->cs = 0.17;
+    c->mu_min = 1e-12; c->mu_max = 1e12;
+    c->relaxation = 1.;
+}
+
+int orc_solver_set_viscosity(OrcSolver *s, const OrcViscosity *c) {
+    ORC_TRY(ensure_init());
+    if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
+    SolverState &st = s->st;
+    SolverState::Viscosity &V = st.vis;
+    if (!c) {  // back to the constant mu: k_diffusion's a_di and wall terms, nothing of the arm is launched from here on
+        const bool was_on = V.on;
+        ORC_HIP(hipStreamSynchronize(ctx().stream));
+        V = SolverState::Viscosity();
+        if (was_on) ORC_TRY(k_diffusion(st));
+        return ORC_OK;
+    }
+    ORC_TRY(validate(*c));
+    // the in-place diagonal mode is the reference's own, with the reference's constant mu (as the transient arm refuses it)
+    if (st.settings.frozen_diagonals == 0) return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: not available with frozen_diagonals = 0");
+    if (c->model == ORC_VISCOSITY_FIELD && !V.has_field)
+        return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: the FIELD model needs orc_solver_set_viscosity_field first");
+    const size_t n = (size_t)std::max<int64_t>(st.n, 1);
+    if (V.mu.n < n) { ORC_TRY(V.mu.alloc(n)); ORC_TRY(V.mu.zero()); }
+    V.c = *c;
+    V.on = true;
+    V.first = true;
+    if (c->model == ORC_VISCOSITY_FIELD) {
+        ORC_TRY(vec_copy(V.mu.p, V.field.p, st.n));
+    } else {
+        ORC_TRY(exchange_velocities(st));
+        ORC_TRY(k_viscosity(st, V.mu.p, nullptr, false));
+    }
+    ORC_TRY(exchange_and_rebuild(st));
+    return status_of(st, "viscosity");
+}
+
+int orc_solver_set_viscosity_field(OrcSolver *s, const double *mu) {
+    ORC_TRY(ensure_init());
+    if (!s || !mu) return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity field: null argument");
+    SolverState &st = s->st;
+    SolverState::Viscosity &V = st.vis;
+    const size_t n = (size_t)st.n;
+    for (size_t i = 0; i < n; ++i)
+        if (!(mu[i] > 0.) || !std::isfinite(mu[i]))
+            return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity field: entry %lld is not positive and finite", (long long)i);
+    const std::vector<int64_t> &g = st.mesh->h_global_ids;
+    if (g.empty()) ORC_TRY(V.field.upload(mu, n));
+    else {
+        std::vector<double> tmp(n);
+        for (size_t c = 0; c < n; ++c) tmp[c] = mu[g[c]];
+        ORC_TRY(V.field.upload(tmp.data(), n));
+    }
+    V.has_field = true;
+    if (V.on && V.c.model == ORC_VISCOSITY_FIELD) {
+        ORC_TRY(vec_copy(V.mu.p, V.field.p, st.n));
+        ORC_TRY(exchange_and_rebuild(st));
+        return status_of(st, "viscosity field");
+    }
+    return ORC_OK;
+}
+
+int orc_solver_get_viscosity(OrcSolver *s, double *mu) {
+    ORC_TRY(ensure_init());
+    if (!s || !mu) return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: null argument");
+    SolverState &st = s->st;
+    if (!st.vis.on) {
+        std::fill(mu, mu + st.n, st.mu);
+        return ORC_OK;
+    }
+    return download_orc_order(st, st.vis.mu.p, mu);
+}
+
+int orc_solver_evaluate_viscosity(OrcSolver *s, double *mu, double *strain_rate) {
+    ORC_TRY(ensure_init());
+    if (!s || !mu) return set_error(ORC_ERR_BAD_ARGUMENT, "evaluate viscosity: null argument");
+    SolverState &st = s->st;
+    if (!st.vis.on) return set_error(ORC_ERR_BAD_ARGUMENT, "evaluate viscosity: the arm is off (orc_solver_set_viscosity)");
+    const size_t n = (size_t)std::max<int64_t>(st.n, 1);
+    DevBuf<double> m_t, g_t;
+    ORC_TRY(m_t.alloc(n)); ORC_TRY(m_t.zero());  // the ghost cells' entries of a partitioned mesh stay zero
+    ORC_TRY(g_t.alloc(n)); ORC_TRY(g_t.zero());
+    ORC_TRY(exchange_velocities(st));
+    ORC_TRY(k_viscosity(st, m_t.p, g_t.p, false));
+    ORC_TRY(download_orc_order(st, m_t.p, mu));
+    if (strain_rate) ORC_TRY(download_orc_order(st, g_t.p, strain_rate));
+    return status_of(st, "evaluate viscosity");
+}
+
+int orc_solver_get_diffusion(OrcSolver *s, double *a_di, double *b_u_di, double *b_v_di, double *b_w_di) {
+    ORC_TRY(ensure_init());
+    if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
+    SolverState &st = s->st;
+    OrcMesh &m = *st.mesh;
+    if (a_di) {
+        DevBuf<double> tmp;
+        ORC_TRY(tmp.ensure((size_t)std::max<int64_t>(m.pat.nnz, 1)));
+        ORC_TRY(sell_export_values(m.pat, st.a_di.p, tmp.p));
+        ORC_TRY(tmp.download(a_di, (size_t)m.pat.nnz));
+    }
+    const size_t n = (size_t)st.n;
+    if (b_u_di) ORC_TRY(st.b_u_di.download(b_u_di, n));
+    if (b_v_di) ORC_TRY(st.b_v_di.download(b_v_di, n));
+    if (b_w_di) ORC_TRY(st.b_w_di.download(b_w_di, n));
+    return ORC_OK;
+}
+
+int orc_bench_viscosity(OrcSolver *s, int reps, double avg_ms[2]) {
+    ORC_TRY(ensure_init());
+    if (!s || !avg_ms) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
+    SolverState &st = s->st;
+    if (!st.vis.on) return set_error(ORC_ERR_BAD_ARGUMENT, "bench viscosity: the arm is off (orc_solver_set_viscosity)");
+    if (reps < 1) reps = 1;
+    DevBuf<double> scratch;  // the law pass writes here: the solver's field keeps its bits; the rebuild rewrites a_di with the same values
+    ORC_TRY(scratch.alloc((size_t)std::max<int64_t>(st.n, 1)));
+    ORC_TRY(scratch.zero());
+    hipEvent_t e0, e1;
+    ORC_HIP(hipEventCreate(&e0));
+    ORC_HIP(hipEventCreate(&e1));
+    int status = ORC_OK;
+    for (int pass = 0; pass < 2 && status == ORC_OK; ++pass) {
+        auto launch = [&] { return pass == 0 ? k_viscosity(st, scratch.p, nullptr, false) : k_diffusion_var(st); };
+        status = launch();  // warm-up
+        if (status == ORC_OK && hipEventRecord(e0, ctx().stream) != hipSuccess) status = set_error(ORC_ERR_HIP, "hipEventRecord failed");
+        for (int i = 0; i < reps && status == ORC_OK; ++i) status = launch();
+        float ms = 0.f;
+        if (status == ORC_OK && (hipEventRecord(e1, ctx().stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                                 hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+            status = set_error(ORC_ERR_HIP, "timing the viscosity passes failed");
+        avg_ms[pass] = (double)ms / reps;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    ORC_HIP(hipStreamSynchronize(ctx().stream));  // scratch is freed on return
+    return status;
+}
+
+}  // extern "C"

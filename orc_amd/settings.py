@@ -121,3 +121,35 @@ class ScalarSettings(C.Structure):
                 raise AttributeError(k)
             setattr(s, k, v)
         return s
+
+
+class ViscosityModel:  # include/orc_types.h OrcViscosityModel
+    FIELD, POWER_LAW, CARREAU, SMAGORINSKY = 1, 2, 3, 4
+
+
+class ViscosityFace:  # include/orc_types.h OrcViscosityFace
+    ARITHMETIC, HARMONIC = 0, 1
+
+
+class Viscosity(C.Structure):
+    """OrcViscosity: a per-cell viscosity in the momentum diffusion (Solver.set_viscosity) — a prescribed field or a law of the
+    strain-rate magnitude g: POWER_LAW k g^(n-1), CARREAU mu_inf + (mu_zero - mu_inf) (1 + (lambda g)^2)^((n-1)/2), SMAGORINSKY
+    mu + rho (cs V^(1/3))^2 g; every law clamped to [mu_min, mu_max] and under-relaxed with `relaxation`."""
+    _fields_ = [
+        ("model", C.c_int32), ("face_interpolation", C.c_int32), ("k", C.c_double), ("n", C.c_double),
+        ("mu_zero", C.c_double), ("mu_inf", C.c_double), ("lambda_", C.c_double), ("cs", C.c_double),
+        ("mu_min", C.c_double), ("mu_max", C.c_double), ("relaxation", C.c_double),
+    ]
+
+    @classmethod
+    def make(cls, model, face_interpolation=ViscosityFace.ARITHMETIC, **overrides):
+        """orc_viscosity_default (power law with n = 1, clamp 1e-12 .. 1e12, no relaxation) with the model, the face interpolation and
+        any other field overridden; `lambda_` is the struct's lambda"""
+        s = cls()
+        lib().orc_viscosity_default(C.byref(s))
+        s.model, s.face_interpolation = int(model), int(face_interpolation)
+        for k, v in overrides.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s

@@ -449,6 +449,53 @@ class Solver:
         check(lib().orc_solver_scalar_boundary_flux(self.ptr, _p(out)))
         return out
 
+    # ---------------------------------------------------------------- variable viscosity (orc_solver_set_viscosity)
+    def set_viscosity(self, v=None, raise_on_error=True):
+        """a settings.Viscosity turns the per-cell viscosity on (evaluated on the current fields and a_di rebuilt at once, then ahead
+        of every momentum assembly); None turns it off and puts the constant-mu diffusion matrix back"""
+        st = lib().orc_solver_set_viscosity(self.ptr, C.byref(v) if v is not None else None)
+        if raise_on_error:
+            check(st)
+        return st
+
+    def set_viscosity_field(self, mu, raise_on_error=True):
+        """the FIELD model's data: one viscosity per cell (> 0, finite), cell order as set_fields()"""
+        mu = _f64(mu)
+        st = lib().orc_solver_set_viscosity_field(self.ptr, _p(mu))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def viscosity(self):
+        """the viscosity field the last assembly used (the constant mu while the arm is off), cell order as get_fields()"""
+        mu = np.empty(self.n)
+        check(lib().orc_solver_get_viscosity(self.ptr, _p(mu)))
+        return mu
+
+    def evaluate_viscosity(self, raise_on_error=True):
+        """the law on the current fields, no relaxation, no state change -> (mu, strain-rate magnitude)
+        (raise_on_error=False: (status, mu, strain_rate))"""
+        mu, g = np.zeros(self.n), np.zeros(self.n)
+        st = lib().orc_solver_evaluate_viscosity(self.ptr, _p(mu), _p(g))
+        if raise_on_error:
+            check(st)
+            return mu, g
+        return st, mu, g
+
+    def diffusion(self):
+        """(a_di in the CSR order of the mesh pattern, b_u_di, b_v_di, b_w_di in the mesh's internal cell order): the diffusion
+        matrix and wall terms the next momentum assembly reads"""
+        a = np.empty(self.mesh.nnz)
+        bu, bv, bw = np.empty(self.n), np.empty(self.n), np.empty(self.n)
+        check(lib().orc_solver_get_diffusion(self.ptr, _p(a), _p(bu), _p(bv), _p(bw)))
+        return a, bu, bv, bw
+
+    def bench_viscosity(self, reps=50):
+        """orc_bench_viscosity: (ms per law pass viscosity_cell_k, ms per rebuild diffusion_var_k); needs set_viscosity()"""
+        ms = np.zeros(2)
+        check(lib().orc_bench_viscosity(self.ptr, C.c_int(reps), _p(ms)))
+        return float(ms[0]), float(ms[1])
+
     def surface_report(self, origin=None, raise_on_error=True):
         """orc_solver_surface_report: per-zone force, moment, mass and momentum flow, area and mean pressure of the current
         state -> SurfaceReport (with raise_on_error=False: (status, report)); reads only"""
