@@ -44,7 +44,7 @@ int bicgstab_dev(const MatView &A, const double *b, double *x, uint64_t iteratio
 // the Multigrid arm (amg_cycle.hip, :270-296); smoother: ORC_SOLVER_BICGSTAB (the reference's) or ORC_SOLVER_MULTICOLOR_GS
 int multigrid_arm_dev(const MatView &A, const double *b, double *x, uint64_t iteration_count, double relaxation_factor,
                       double convergence_threshold, int preconditioner, Arena &arena, SolveStats *stats, int smoother);
-// extension: multicolour Gauss-Seidel and GS-preconditioned BiCGSTAB (gs.hip)
+// extension: multicolour Gauss-Seidel and GS-preconditioned BiCGSTAB (gs_sweep.hip)
 int gs_arm_dev(const MatView &A, const double *b, double *x, uint64_t iteration_count, double relaxation_factor, int method, Arena &arena);
 // extension: restarted GMRES (gmres.hip)
 int gmres_dev(const MatView &A, const double *b, double *x, uint64_t iteration_count, double convergence_threshold, Arena &arena,
@@ -70,7 +70,7 @@ int amg_debug_packed(const MatView &A, Arena &arena, int64_t sizes[5], int32_t *
                      int64_t *lptr_h, uint16_t *lidx_h, int32_t *wcol_h, int32_t *wsize_h);
 int amg_debug_xwin_raw(const MatView &A, Arena &arena, int64_t info[10], int64_t *lptr_h, unsigned char *pos_raw_h, int32_t *wcol_raw_h, int32_t *wsize_h,
                        int32_t *wfmt_h);
-// the colouring cache, the sweeps alone and the colouring of a pattern (gs.hip)
+// the colouring cache, the sweeps alone and the colouring of a pattern (gs_coloring.hip, gs_sweep.hip, gs_slot.hip)
 void gs_forget_pattern(const void *col_ptr);
 int bench_gs_sweep_dev(const MatView &A, const double *b, double *x, int reps, Arena &arena, float *ms_per_sweep, int *n_colors);
 int bench_gs_sweep0_dev(const MatView A[3], const double *const b[3], int reps, Arena &arena, float ms[2], int *n_colors);

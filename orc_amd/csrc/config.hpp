@@ -39,7 +39,7 @@ struct Config {
     bool xwin_wg_per_block = true;      // ORC_XWIN_WG_PER_BLOCK: window products launch one workgroup per 256-row block and fold their sums inside the launch (0: 2 048 persistent workgroups, r04)
     bool xwin_level_cap = true;         // ORC_XWIN_LEVEL_CAP: a level's products size their LDS window to what the level needs (0: the compiled 40 KB, as until r04)
     bool xwin_compact = true;           // ORC_XWIN_COMPACT: 12-bit window positions on levels whose LDS share is <= 4 096 entries, 16-bit window columns per block (0: 16 / 32 bits, as until r07)
-    // ---- Gauss-Seidel extension (gs.hip)
+    // ---- Gauss-Seidel extension (gs_*.hip)
     bool gs_slotspace = true;           // ORC_GS_SLOTSPACE: GS-preconditioned BiCGSTAB in colour-sorted slot space (0: row space, as partitioned runs use)
     // ---- diagnostics (stderr; none touches a result)
     bool trace = false;                 // ORC_DEBUG_TRACE: progress markers of the SIMPLE driver and the solves

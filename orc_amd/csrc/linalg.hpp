@@ -374,7 +374,7 @@ int multigrid_arm3_dev(const MatView3 &A3, const double *const b[3], double *con
                        double convergence_threshold, int preconditioner, Arena &arena, TripleLane lanes[3], SiblingPairing *sibling, int status_out[3],
                        const std::function<void()> &on_hierarchies_built = nullptr);  // called once, from the calling thread, when the three set-ups are through
 
-// [r04] multicolour-GS-preconditioned BiCGSTAB (extension, gs.hip) for the three momentum systems in lock-step on the mesh pattern
+// [r04] multicolour-GS-preconditioned BiCGSTAB (extension, gs_slot.hip) for the three momentum systems in lock-step on the mesh pattern
 // (BASELINE configs[2]); b[k], x[k] in row order, x in / out; single GPU.  gs_slot_space_enabled: ORC_GS_SLOTSPACE != 0.
 int gs_bicgstab3_dev(const MatView A[3], const double *const b[3], double *const x[3], uint64_t iteration_count, Arena &arena);
 bool gs_slot_space_enabled();

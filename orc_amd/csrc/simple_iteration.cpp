@@ -348,7 +348,7 @@ static int solve_momentum_triple(SolverState &s, const std::function<void()> &on
     const double *b[3] = {s.b_u.p, s.b_v.p, s.b_w.p};
     double *x[3] = {s.u.p, s.v.p, s.w.p};
     if (s.arena.empty()) ORC_TRY(s.arena.reset());
-    if (t.solver_type == ORC_SOLVER_BICGSTAB_GS_PRECOND) {  // [r04] BASELINE configs[2]: u, v, w per colour in ONE launch (gs.hip, slot space)
+    if (t.solver_type == ORC_SOLVER_BICGSTAB_GS_PRECOND) {  // [r04] BASELINE configs[2]: u, v, w per colour in ONE launch (gs_slot.hip, slot space)
         ArenaScope scope(s.arena);
         MatView V[3];
         const double *bb[3];

@@ -1,6 +1,6 @@
 """Case table of the Gauss-Seidel tests (tests/test_gs_cases_cpu.py, tests/test_gpu_gs_cases.py).
 
-The Gauss-Seidel arms of orc_amd/csrc/gs.hip (the multicolour sweep, the GS-preconditioned BiCGSTAB in row and in slot space,
+The Gauss-Seidel arms of orc_amd/csrc/gs_*.hip (the multicolour sweep, the GS-preconditioned BiCGSTAB in row and in slot space,
 the smoother of MULTIGRID_GS) colour the pattern on the device, sort it by colour into 64-row slices and sweep slice ranges.
 The matrices here sit where that can go wrong on a USER matrix: patterns that are not structurally symmetric (a row with an
 in-neighbour it does not store), colours of fewer than 64 rows, exactly 64 colours and one more, more than 1 024 row blocks and

@@ -1,4 +1,4 @@
-"""Plain numpy restatements of what orc_amd/csrc/gs.hip computes, for tests/test_gs_cases_cpu.py and tests/test_gpu_gs_cases.py.
+"""Plain numpy restatements of what orc_amd/csrc/gs_*.hip compute (colouring: gs_coloring.hip, sweep and row-space arm: gs_sweep.hip), for tests/test_gs_cases_cpu.py and tests/test_gpu_gs_cases.py.
 The library is not imported.
 
   color_today(a)    the colouring rule that looks at a row's own line alone (the rule of the library before it learned about

@@ -133,7 +133,7 @@ def test_solve_steady_with_gs_preconditioned_bicgstab(gpu, oracle, mesh_path):
 
 
 def test_slot_space_solver_follows_the_row_space_recurrences(gpu, monkeypatch):
-    """[r04] The GS-preconditioned BiCGSTAB now lives in the colour-sorted numbering (gs.hip: gsx_*): vectors permuted once, the
+    """[r04] The GS-preconditioned BiCGSTAB now lives in the colour-sorted numbering (gs_slot.hip: gsx_*): vectors permuted once, the
     preconditioner sweep from zero without a zero fill (columns of the colour's own and later colours are skipped: exact zeros),
     sums folded by their consumers.  Row sums and sweeps keep their bits; only the partial sums group rows differently, so after a few
     iterations the two forms agree to rounding (ORC_GS_SLOTSPACE=0 = r03's row-space form), with and without the Jacobi scaling, and
@@ -162,12 +162,14 @@ def test_gs_momentum_systems_in_lock_step_are_bit_identical_to_their_own_solves(
     """u, v, w per colour in ONE launch (interleaved slot-space vectors, three value streams on the shared colour-sorted pattern):
     whole SIMPLE iterations with BASELINE configs[2]'s solver are bit-identical to the runs that solve the systems one at a time
     (ORC_TRIPLE_MOMENTUM=0: three lanes, same kernels with S = 1), frozen systems included (w == 0 exactly on the one-cell-deep
-    channel: its solve breaks down at once and the guard freezes it while u and v carry on)."""
+    channel: its solve breaks down at once and the guard freezes it while u and v carry on).  The 48 x 40 x 36 channel has 1 080
+    row blocks and at least as many colour-sorted slices: the mesh pattern's layout (build_sorted_layout, gs_layout.hip) goes through
+    the carry branches of its two 1 024-wide scans."""
     import helpers as H
     from orc_amd.mesh import Mesh, hex_channel, set_channel_bcs
     from orc_amd.settings import NumericalSettings
     from orc_amd.solver import solve_steady
-    for shape, w_zero in (((24, 16, 10), False), ((40, 30, 1), True)):
+    for shape, w_zero in (((24, 16, 10), False), ((40, 30, 1), True), ((48, 40, 36), False)):
         a = set_channel_bcs(hex_channel(*shape))
         s = NumericalSettings.default(momentum=4, solver_type=BICGSTAB_GS, iterations=12)
         out = []
@@ -176,15 +178,17 @@ def test_gs_momentum_systems_in_lock_step_are_bit_identical_to_their_own_solves(
             u, v, w, p = H.seeded_fields(a, seed=8, scale_u=4e-4, w_zero=w_zero)
             solve_steady(Mesh(a), u, v, w, p, s, 1000.0, 1e-3, 3)
             out.append((u, v, w, p))
-        assert np.isfinite(out[0][0]).all()
+        for x in out[0]:
+            assert np.isfinite(x).all(), shape
+        assert not np.array_equal(out[0][0], H.seeded_fields(a, seed=8, scale_u=4e-4, w_zero=w_zero)[0]), shape
         for x, y in zip(*out):
             assert np.array_equal(x, y), shape
 
 
 def test_gs_momentum_systems_in_lock_step_off_the_hex_channel(gpu, oracle, mesh_path, monkeypatch):
     """The same comparison on the prism / hex checker mesh (meshgen.write_mixed_channel_msh(path, 6, 4, 3, split="checker")): rows of 4, 5
-    and 6 neighbours in one pattern, and every colour has fewer than 64 rows, so every slice of the host-built colour-sorted layout
-    (build_color_sell) is partly padding — the slots whose rowid is -1 take part in every launch of the lock-step solve."""
+    and 6 neighbours in one pattern, and every colour has fewer than 64 rows, so every slice of the mesh pattern's colour-sorted layout
+    (build_sorted_layout, gs_layout.hip) is partly padding — the slots whose rowid is -1 take part in every launch of the lock-step solve."""
     import helpers as H
     import scipy.sparse as sp
     from orc_amd.linear_algebra import debug_coloring

@@ -1,6 +1,6 @@
-"""The Gauss-Seidel arms (orc_amd/csrc/gs.hip) on user matrices, at their edges: the matrices of tests/gs_cases.py — patterns that
+"""The Gauss-Seidel arms (orc_amd/csrc/gs_*.hip) on user matrices, at their edges: the matrices of tests/gs_cases.py — patterns that
 are not structurally symmetric, colours of fewer than 64 rows, exactly 64 colours and one too many, more than 1 024 row blocks
-and colour-sorted slices (the carry branches of gs_column_scan_k and gs_slice_ptr_k), rows of 1 ... 130 entries, an empty row,
+and colour-sorted slices (the carry branches of gs_column_scan_k and gs_slice_ptr_k in gs_layout.hip), rows of 1 ... 130 entries, an empty row,
 a last slice with one live row — against the numpy restatements of tests/gs_restatement.py, which tests/test_gs_cases_cpu.py
 checks against forward substitution without a GPU.
 
