@@ -532,6 +532,35 @@ int orc_solver_get_diffusion(OrcSolver *s, double *a_di /*[nnz]*/, double *b_u_d
  * (viscosity_cell_k, into scratch), avg_ms[1] the rebuild (diffusion_var_k); needs the arm on, changes no bit of the solver */
 int orc_bench_viscosity(OrcSolver *s, int reps, double avg_ms[2]);
 
+/* ---------- wall distance and wall damping (new-build extension, orc_types.h OrcWallDamping) ----------
+ * The wall faces of a mesh are the boundary faces of owned cells whose zone is a wall: zone_is_wall[n_zones] != 0, or with
+ * zone_is_wall == NULL the zones of type ORC_BC_WALL.  The wall distance of a cell is the distance to the plane of the wall face whose
+ * centroid is nearest to the cell's centroid; among faces that tie exactly in that squared centroid distance the smallest plane
+ * distance wins (DESIGN.md §3 "Wall distance and wall damping": operator order, the approximation next to convex wall edges).  The
+ * value depends on the set of wall faces only: not on their order, the cell numbering or a partition.  A mesh without a wall face
+ * gives +inf.
+ *  - orc_mesh_wall_distance: d in the cell order of orc_solver_get_fields (ORC order on a reordered mesh); the ghost entries of a
+ *    partitioned mesh are 0.  The field is searched at first use and kept on the mesh, keyed by the resolved wall mask;
+ *    orc_mesh_update_zones / orc_mesh_sync_zones drop it when the wall-ness of a zone changes.  On a partitioned mesh every rank calls
+ *    it (the ranks' wall tables are gathered with two all-reduces).
+ *  - orc_solver_set_wall_damping: checks w and stores it on the solver; it takes effect whenever the viscosity model is SMAGORINSKY
+ *    (the wall distance of the default mask is then read by the law pass).  With SMAGORINSKY on, the field is re-evaluated at once
+ *    without relaxation, as orc_solver_set_viscosity does.  w == NULL or mode NONE: the undamped law, bit for bit.  Refused with
+ *    ORC_ERR_BAD_ARGUMENT and the solver unchanged: a value that is not finite, kappa (MIN), a_plus or u_tau (VAN_DRIEST) <= 0, an
+ *    unknown mode, reserved0 != 0.
+ *  - orc_solver_get_wall_damping: the stored setting; *enabled = 1 when its mode is not NONE.
+ *  - orc_debug_wall_distance: the search without the cache; cull = 0 walks every table entry for every cell.
+ *  - orc_debug_wall_search: out = {wall faces over all ranks, tile length T, tiles, tile visits summed over waves, waves}: the table
+ *    of the last search and the visits and waves of all searches since the last reset (reset != 0 clears them after the read).
+ *  - orc_bench_wall_distance: HIP-event average ms of `reps` launches of the search kernel alone on the default mask's table. */
+int orc_mesh_wall_distance(OrcMesh *m, const int32_t *zone_is_wall /*[n_zones], NULL = type WALL*/, double *d /*[n_cells]*/);
+void orc_wall_damping_default(OrcWallDamping *w);
+int orc_solver_set_wall_damping(OrcSolver *s, const OrcWallDamping *w /*NULL = off*/);
+int orc_solver_get_wall_damping(OrcSolver *s, OrcWallDamping *w, int32_t *enabled);
+int orc_debug_wall_distance(OrcMesh *m, const int32_t *zone_is_wall, int cull, double *d /*[n_cells]*/);
+int orc_debug_wall_search(long long out[5], int reset);
+int orc_bench_wall_distance(OrcMesh *m, int cull, int reps, double *avg_ms);
+
 /* ---------- measurement hooks (bench.py): HIP-event timed launches of single kernels ---------- */
 /* y = A x with the momentum matrix a_u of the solver, `reps` launches; returns average ms per launch */
 int orc_bench_spmv(OrcSolver *s, int reps, double *avg_ms, double *checksum);

@@ -305,6 +305,19 @@ typedef struct OrcViscosity {
     double relaxation;          /* (0, 1]: the stored field becomes mu_old + w (mu - mu_old); 1 = none, no arithmetic */
 } OrcViscosity;
 
+/* Wall damping of the Smagorinsky length (new-build extension; orc_amd.h: orc_solver_set_wall_damping): with d the wall distance of the
+ * cell (orc_mesh_wall_distance, zones of type WALL) and l0 = cs * cbrt(V_P), the law's length l becomes
+ *   MIN:        l = fmin(kappa * d, l0)
+ *   VAN_DRIEST: yp = ((rho * u_tau) * d) / mu;  l = l0 * (-expm1(-(yp / a_plus)))
+ * DESIGN.md §3 "Wall distance and wall damping" fixes the operator order. */
+enum OrcWallDampingMode { ORC_WALL_DAMPING_NONE = 0, ORC_WALL_DAMPING_MIN = 1, ORC_WALL_DAMPING_VAN_DRIEST = 2 };
+typedef struct OrcWallDamping {
+    int32_t mode, reserved0; /* OrcWallDampingMode; reserved0 = 0 */
+    double kappa;            /* MIN: > 0, default 0.41 */
+    double a_plus;           /* VAN_DRIEST: > 0, default 26 */
+    double u_tau;            /* VAN_DRIEST: > 0, the caller's friction velocity (channel: sqrt(h |dp/dx| / rho)); default 0 */
+} OrcWallDamping;            /* 32 bytes */
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,23 @@ def lib():
             L.orc_solver_get_diffusion.restype = C.c_int
             L.orc_bench_viscosity.argtypes = [C.c_void_p, C.c_int, _f64]
             L.orc_bench_viscosity.restype = C.c_int
+        # wall distance and wall damping (orc_amd.h "wall distance and wall damping"): full signatures
+        if hasattr(L, "orc_mesh_wall_distance"):
+            _f64, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+            L.orc_mesh_wall_distance.argtypes = [C.c_void_p, _i32, _f64]
+            L.orc_mesh_wall_distance.restype = C.c_int
+            L.orc_debug_wall_distance.argtypes = [C.c_void_p, _i32, C.c_int, _f64]
+            L.orc_debug_wall_distance.restype = C.c_int
+            L.orc_debug_wall_search.argtypes = [C.POINTER(C.c_longlong), C.c_int]
+            L.orc_debug_wall_search.restype = C.c_int
+            L.orc_bench_wall_distance.argtypes = [C.c_void_p, C.c_int, C.c_int, _f64]
+            L.orc_bench_wall_distance.restype = C.c_int
+            L.orc_wall_damping_default.argtypes = [C.c_void_p]
+            L.orc_wall_damping_default.restype = None
+            L.orc_solver_set_wall_damping.argtypes = [C.c_void_p, C.c_void_p]
+            L.orc_solver_set_wall_damping.restype = C.c_int
+            L.orc_solver_get_wall_damping.argtypes = [C.c_void_p, C.c_void_p, _i32]
+            L.orc_solver_get_wall_damping.restype = C.c_int
         # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
         if hasattr(L, "orc_debug_amg_setup_stats"):
             L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]

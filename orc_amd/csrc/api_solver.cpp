@@ -158,6 +158,7 @@ int orc_mesh_cell_order(const OrcMesh *m, int64_t *global_ids) {
 
 int orc_mesh_update_zones(OrcMesh *m, const int32_t *zone_type, const double *zone_scalar, const double *zone_vector) {
     if (!m) return set_error(ORC_ERR_BAD_ARGUMENT, "null mesh");
+    if (zone_type) wall_zones_changed(*m, zone_type);  // the cached wall distance goes when the wall-ness of a zone changes
     ORC_TRY(m->ztype.upload(zone_type, (size_t)m->n_zones));
     ORC_TRY(m->zscal.upload(zone_scalar, (size_t)m->n_zones));
     ORC_TRY(m->zvec.upload(zone_vector, (size_t)3 * m->n_zones));

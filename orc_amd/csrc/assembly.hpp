@@ -39,6 +39,19 @@ struct SurfaceIndex {
     DevBuf<int> status;
 };
 
+// The wall table of one wall mask and the distance field searched from it (wall_distance.hip): built at a mesh's first use, kept
+// until the wall-ness of a zone changes (orc_mesh_update_zones).  The table holds the wall faces of ALL ranks, SoA, this rank's
+// ascending in face id; tile t covers the entries [t * kWallTile, (t + 1) * kWallTile) and carries a bounding sphere of their centroids.
+struct WallDistance {
+    std::vector<int32_t> mask;   // [Z] the resolved mask the table was built for
+    bool from_types = false;     // the mask is the default one (type WALL): a change of zone types can invalidate it
+    int64_t n_wall = 0, n_tiles = 0;
+    DevBuf<double> table;        // [6][n_wall]: centroid x, y, z, normal x, y, z
+    DevBuf<double> tiles;        // [4][n_tiles]: sphere centre x, y, z and (widened) radius
+    DevBuf<double> d;            // [n_cells] internal cell order, ghost entries 0
+    bool searched = false;       // d holds the field
+};
+
 #ifdef __HIPCC__
 // the TVD limiters of settings::MomentumDiscretization (lib.rs:107-118): momentum_k and the scalar arm's scalar_face_k
 __device__ __forceinline__ double psi_eval(int momentum, double r) {
@@ -74,6 +87,7 @@ struct OrcMesh {
     std::vector<int64_t> h_global_ids;      // orc_mesh_create_reordered: ORC index of every internal cell (empty = identity);
                                             // orc_solver_set_fields / get_fields / orc_solve_steady permute through it
     std::unique_ptr<orc::SurfaceIndex> surface;  // null until the first surface report (surface.hip)
+    std::unique_ptr<orc::WallDistance> wall;     // null until the first wall distance (wall_distance.hip)
     orc::MeshDev dev() const;
 };
 
@@ -221,6 +235,7 @@ struct SolverState {
         bool first = true;      // the next evaluation of an assembly takes the law's value itself (no relaxation)
         DevBuf<double> snap_mu;
         bool snap_on = false, snap_first = true;
+        OrcWallDamping wd{ORC_WALL_DAMPING_NONE, 0, 0.41, 26., 0.};  // wall damping of the Smagorinsky length (orc_solver_set_wall_damping); mode NONE = off
     } vis;
     const double *cell_viscosity() const { return vis.on ? vis.mu.p : nullptr; }  // what the surface reports and boundary maps take
 };
@@ -305,6 +320,12 @@ void monitor_append(SolverState &s);
 int k_viscosity(SolverState &s, double *mu_out, double *g_out, bool relax);
 int k_diffusion_var(SolverState &s);
 int k_viscosity_update(SolverState &s);
+// wall distance (wall_distance.hip): the cached field of the default mask (zones of type WALL) in the mesh's internal cell order, searched
+// at first use; synchronises and, on a partitioned mesh, runs two all-reduces when it has to build.  wall_zones_changed: what
+// orc_mesh_update_zones calls with the new zone types before it uploads them.
+int wall_distance_default(OrcMesh &m, const double **d_dev);
+void wall_zones_changed(OrcMesh &m, const int32_t *zone_type);
+int wall_damping_validate(const OrcWallDamping &w);  // ORC_ERR_BAD_ARGUMENT with a message, or ORC_OK
 
 }  // namespace orc
 

@@ -5,7 +5,9 @@
 //   viscosity_cell_k   one thread per owned cell, derived_cell_k's XCD-contiguous block walk: the velocity gradient of the settings'
 //                      reconstruction by the assembly's own per-cell body (gradient_cell.hpp), g = strain_rate_mag(strain_ss(G)) — the
 //                      bits of ORC_DERIVED_STRAIN_RATE_MAG — then the law, the clamp and the relaxation; writes mu and, for
-//                      orc_solver_evaluate_viscosity, g.  Model and relaxation are wave-uniform arguments.
+//                      orc_solver_evaluate_viscosity, g.  Model and relaxation are wave-uniform arguments.  With wall damping of the
+//                      Smagorinsky length (orc_solver_set_wall_damping) the "damped" instantiation also reads the cell's wall distance
+//                      (wall_distance.hip) — DESIGN.md §3 "Wall distance and wall damping".
 //   diffusion_var_k    one thread per owned row, the same walk: diffusion_k's loop (assembly.hip) with mu replaced by the face
 //                      viscosity, i.e. one more gather (mu_N) per interior face; writes a_di, b_u_di, b_v_di, b_w_di
 // momentum_k reads the diffusion coefficients from a_di and the wall terms from b_*_di and never sees mu: neither it, nor the Rhie-Chow
@@ -49,11 +51,19 @@ struct ViscosityArgs {
     int model, relax;     // the same in every lane
     double k, n, mu_zero, mu_inf, lambda, cs, mu_min, mu_max, relaxation;
     double rho, mu_lam;   // the solver's density and (laminar) viscosity: SMAGORINSKY
+    // wall damping of the Smagorinsky length (OrcWallDamping): the mode (the same in every lane) and the wall distance per cell, null
+    // unless the mode needs it
+    int damping;
+    const double *wall_d;
+    double kappa, a_plus, u_tau;
 };
 
 // The law at strain-rate magnitude g in a cell of volume vol, then the clamp: THE operator order of DESIGN §3 "Variable viscosity".
-// g = 0 with n < 1 makes pow return +inf, which the clamp turns into mu_max: intended.
-__device__ __forceinline__ double viscosity_law(const ViscosityArgs &A, double g, double vol) {
+// g = 0 with n < 1 makes pow return +inf, which the clamp turns into mu_max: intended.  d: the cell's wall distance (read by the
+// damped Smagorinsky length only; DESIGN §3 "Wall distance and wall damping"): d = +inf gives l0 exactly in both modes.
+// kDamped = false compiles today's undamped sequence alone: the kernel of a solver without damping is the one it was.
+template <bool kDamped>
+__device__ __forceinline__ double viscosity_law(const ViscosityArgs &A, double g, double vol, double d) {
     double m;
     if (A.model == ORC_VISCOSITY_POWER_LAW) {
         m = A.k * pow(g, A.n - 1.);
@@ -61,14 +71,22 @@ __device__ __forceinline__ double viscosity_law(const ViscosityArgs &A, double g
         const double t = A.lambda * g;
         m = A.mu_inf + (A.mu_zero - A.mu_inf) * pow(1. + t * t, (A.n - 1.) / 2.);
     } else {  // SMAGORINSKY
-        const double l = A.cs * cbrt(vol);
+        double l = A.cs * cbrt(vol);
+        if (kDamped) {
+            if (A.damping == ORC_WALL_DAMPING_MIN) {
+                l = fmin(A.kappa * d, l);
+            } else if (A.damping == ORC_WALL_DAMPING_VAN_DRIEST) {
+                const double yp = ((A.rho * A.u_tau) * d) / A.mu_lam;
+                l = l * (-expm1(-(yp / A.a_plus)));  // expm1: no cancellation at the wall
+            }
+        }
         m = A.mu_lam + (A.rho * (l * l)) * g;
     }
     return fmin(fmax(m, A.mu_min), A.mu_max);
 }
 
 // Reads what grad_u_k / grad_u_lsq_k read; writes one double per cell (two for orc_solver_evaluate_viscosity).
-template <bool kLsq>
+template <bool kLsq, bool kDamped>
 __global__ __launch_bounds__(kBlock) void viscosity_cell_k(MeshDev M, ViscosityArgs A, int *status) {
     const int n_items = (int)M.n_own;  // cell ids are int32 (MeshDev.c0)
     for (BlockWalk W = block_walk(n_items); W.vb < W.vb_end; W.vb += W.vb_step) {
@@ -89,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void viscosity_cell_k(MeshDev M, ViscosityA
         if (A.model == ORC_VISCOSITY_FIELD) {
             mu = A.field[c];
         } else {
-            mu = viscosity_law(A, g, M.vol[c]);
+            mu = viscosity_law<kDamped>(A, g, M.vol[c], kDamped ? A.wall_d[c] : INFINITY);
             if (A.relax) {
                 const double old = A.mu[c];
                 mu = old + A.relaxation * (mu - old);
@@ -210,11 +228,19 @@ int k_viscosity(SolverState &s, double *mu_out, double *g_out, bool relax) {
     A.k = c.k; A.n = c.n; A.mu_zero = c.mu_zero; A.mu_inf = c.mu_inf; A.lambda = c.lambda; A.cs = c.cs;
     A.mu_min = c.mu_min; A.mu_max = c.mu_max; A.relaxation = c.relaxation;
     A.rho = s.rho; A.mu_lam = s.mu;
+    const OrcWallDamping &wd = s.vis.wd;
+    A.damping = ORC_WALL_DAMPING_NONE;
+    A.wall_d = nullptr;
+    A.kappa = wd.kappa; A.a_plus = wd.a_plus; A.u_tau = wd.u_tau;
+    if (c.model == ORC_VISCOSITY_SMAGORINSKY && wd.mode != ORC_WALL_DAMPING_NONE) {
+        A.damping = wd.mode;
+        ORC_TRY(wall_distance_default(m, &A.wall_d));  // the mesh's cached field; searched here at first use
+    }
     const int g = grid_for(s.n_own);
-    if (s.settings.gradient_reconstruction == ORC_GRAD_LEAST_SQUARES)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(viscosity_cell_k<true>), dim3(g), dim3(kBlock), 0, ctx().stream, m.dev(), A, s.dev_status.p);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(viscosity_cell_k<false>), dim3(g), dim3(kBlock), 0, ctx().stream, m.dev(), A, s.dev_status.p);
+    const bool lsq = s.settings.gradient_reconstruction == ORC_GRAD_LEAST_SQUARES, damped = A.wall_d != nullptr;
+    auto kernel = lsq ? (damped ? viscosity_cell_k<true, true> : viscosity_cell_k<true, false>)
+                      : (damped ? viscosity_cell_k<false, true> : viscosity_cell_k<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(g), dim3(kBlock), 0, ctx().stream, m.dev(), A, s.dev_status.p);
     ORC_HIP(hipGetLastError());
     return ORC_OK;
 }
@@ -269,7 +295,9 @@ int orc_solver_set_viscosity(OrcSolver *s, const OrcViscosity *c) {
     if (!c) {  // back to the constant mu: k_diffusion's a_di and wall terms, nothing of the arm is launched from here on
         const bool was_on = V.on;
         ORC_HIP(hipStreamSynchronize(ctx().stream));
+        const OrcWallDamping wd = V.wd;  // the damping setting is the solver's, not the arm's: it waits for the next SMAGORINSKY
         V = SolverState::Viscosity();
+        V.wd = wd;
         if (was_on) ORC_TRY(k_diffusion(st));
         return ORC_OK;
     }
@@ -291,6 +319,27 @@ int orc_solver_set_viscosity(OrcSolver *s, const OrcViscosity *c) {
     }
     ORC_TRY(exchange_and_rebuild(st));
     return status_of(st, "viscosity");
+}
+
+int orc_solver_set_wall_damping(OrcSolver *s, const OrcWallDamping *w) {
+    ORC_TRY(ensure_init());
+    if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
+    SolverState &st = s->st;
+    SolverState::Viscosity &V = st.vis;
+    OrcWallDamping next = V.wd;
+    if (w) {
+        ORC_TRY(wall_damping_validate(*w));
+        next = *w;
+    } else {
+        next.mode = ORC_WALL_DAMPING_NONE;
+    }
+    V.wd = next;
+    if (!V.on || V.c.model != ORC_VISCOSITY_SMAGORINSKY) return ORC_OK;  // takes effect when SMAGORINSKY is switched on
+    V.first = true;
+    ORC_TRY(exchange_velocities(st));
+    ORC_TRY(k_viscosity(st, V.mu.p, nullptr, false));
+    ORC_TRY(exchange_and_rebuild(st));
+    return status_of(st, "wall damping");
 }
 
 int orc_solver_set_viscosity_field(OrcSolver *s, const double *mu) {

@@ -164,6 +164,14 @@ def set_mixed_channel_bcs(a, top_wall_velocity=0.0, dp_dx=5.0, dx=0.002):
     return a
 
 
+def wall_search_stats(reset=False):
+    """orc_debug_wall_search -> dict(wall_faces, tile, tiles, tile_visits, waves): the table of the last wall-distance search and the
+    tile visits and waves of all searches since the last reset"""
+    out = (C.c_longlong * 5)()
+    check(lib().orc_debug_wall_search(out, C.c_int(1 if reset else 0)))
+    return dict(zip(("wall_faces", "tile", "tiles", "tile_visits", "waves"), (int(x) for x in out)))
+
+
 class Mesh:
     """Device-resident mesh (OrcMesh*)."""
 
@@ -219,6 +227,38 @@ class Mesh:
         faces = np.zeros(max(int(zp[-1]), 1), np.int32)
         check(lib().orc_mesh_boundary_index(self.ptr, zp.ctypes.data_as(_I64), faces.ctypes.data_as(_I32), C.byref(nb), C.byref(chunk)))
         return zp, faces[:int(zp[-1])], int(nb.value), int(chunk.value)
+
+    def _wall_mask(self, zones):
+        """zones: None (the zones of type Wall) or a list of zone names or indices -> int32 mask per zone, or None"""
+        if zones is None:
+            return None
+        mask = np.zeros(len(self.arrays["zone_type"]), np.int32)
+        for z in zones:
+            mask[list(self.arrays["zone_names"]).index(z) if isinstance(z, str) else int(z)] = 1
+        return mask
+
+    def wall_distance(self, zones=None):
+        """orc_mesh_wall_distance: per cell the distance to the plane of the wall face with the nearest centroid (+inf without a wall
+        face; the ghost entries of a partitioned mesh are 0), cell order as Solver.get_fields().  zones: the wall zones by name or
+        index, None = the zones of type Wall.  Searched on the device at first use and kept until update_zones() changes a wall."""
+        mask = self._wall_mask(zones)
+        d = np.zeros(self.n_cells)
+        check(lib().orc_mesh_wall_distance(self.ptr, None if mask is None else mask.ctypes.data_as(_I32), d.ctypes.data_as(_F64)))
+        return d
+
+    def debug_wall_distance(self, zones=None, cull=True):
+        """orc_debug_wall_distance: the same search past the cache; cull=False walks the whole wall table for every cell"""
+        mask = self._wall_mask(zones)
+        d = np.zeros(self.n_cells)
+        check(lib().orc_debug_wall_distance(self.ptr, None if mask is None else mask.ctypes.data_as(_I32), C.c_int(1 if cull else 0),
+                                            d.ctypes.data_as(_F64)))
+        return d
+
+    def bench_wall_distance(self, cull=True, reps=5):
+        """orc_bench_wall_distance: HIP-event ms per launch of the search kernel on the default mask's table"""
+        ms = C.c_double(0.0)
+        check(lib().orc_bench_wall_distance(self.ptr, C.c_int(1 if cull else 0), C.c_int(reps), C.byref(ms)))
+        return ms.value
 
     def matrix_pattern(self):
         rp = np.empty(self.n_cells + 1, np.int64)

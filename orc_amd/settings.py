@@ -153,3 +153,25 @@ class Viscosity(C.Structure):
                 raise AttributeError(k)
             setattr(s, k, v)
         return s
+
+
+class WallDampingMode:  # include/orc_types.h OrcWallDampingMode
+    NONE, MIN, VAN_DRIEST = 0, 1, 2
+
+
+class WallDamping(C.Structure):
+    """OrcWallDamping: wall damping of the Smagorinsky length l0 = cs V^(1/3) with the wall distance d (Solver.set_wall_damping) —
+    MIN l = min(kappa d, l0); VAN_DRIEST l = l0 (1 - exp(-y+ / a_plus)), y+ = rho u_tau d / mu with the caller's friction velocity."""
+    _fields_ = [("mode", C.c_int32), ("reserved0", C.c_int32), ("kappa", C.c_double), ("a_plus", C.c_double), ("u_tau", C.c_double)]
+
+    @classmethod
+    def make(cls, mode, **overrides):
+        """orc_wall_damping_default (kappa 0.41, a_plus 26, u_tau 0) with the mode and any other field overridden"""
+        s = cls()
+        lib().orc_wall_damping_default(C.byref(s))
+        s.mode = int(mode)
+        for k, v in overrides.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s

@@ -458,6 +458,21 @@ class Solver:
             check(st)
         return st
 
+    def set_wall_damping(self, w=None, raise_on_error=True):
+        """a settings.WallDamping damps the Smagorinsky length with the wall distance of the zones of type Wall (in effect whenever the
+        viscosity model is SMAGORINSKY; the field is re-evaluated at once if it is); None turns the damping off"""
+        st = lib().orc_solver_set_wall_damping(self.ptr, C.byref(w) if w is not None else None)
+        if raise_on_error:
+            check(st)
+        return st
+
+    def wall_damping(self):
+        """orc_solver_get_wall_damping -> (settings.WallDamping as stored, enabled)"""
+        from .settings import WallDamping
+        w, on = WallDamping(), C.c_int32(0)
+        check(lib().orc_solver_get_wall_damping(self.ptr, C.byref(w), C.byref(on)))
+        return w, bool(on.value)
+
     def set_viscosity_field(self, mu, raise_on_error=True):
         """the FIELD model's data: one viscosity per cell (> 0, finite), cell order as set_fields()"""
         mu = _f64(mu)
