@@ -561,6 +561,55 @@ int orc_debug_wall_distance(OrcMesh *m, const int32_t *zone_is_wall, int cull, d
 int orc_debug_wall_search(long long out[5], int reset);
 int orc_bench_wall_distance(OrcMesh *m, int cull, int reps, double *avg_ms);
 
+/* ---------- running time statistics (new-build extension, orc_types.h OrcTimeStatistics) ----------
+ * Time-averaged fields and the second moments of their fluctuations, accumulated where the fields live (DESIGN.md §3 "Time
+ * statistics" has the definitions and the operator order).  Off by default: a solver that never calls
+ * orc_solver_set_time_statistics launches exactly what it launched before and allocates nothing new.  Read-only towards the flow:
+ * with the arm on, u, v, w, p, the scalar, the viscosity and every report keep their bits.  One fused streaming pass per sample
+ * (time_stats_k) over K * n_cells accumulators, K = the fields of the enabled groups in OrcStatField order; no atomics, no
+ * reductions: the same samples give the same bits.
+ *  - orc_time_statistics_default: MEAN | STRESS, start_step 1, interval 1.
+ *  - orc_solver_set_time_statistics(s, c): c == NULL turns the arm off and frees its buffers; otherwise validates c and turns the arm
+ *    on with zeroed accumulators, weight sum W = 0, 0 samples and step counter 0.  It does not need the transient arm.
+ *  - orc_solver_advance with the arm on: after each step's SIMPLE iterations (and the scalar solve) the step counter advances, and the
+ *    step is sampled with weight dt when counter >= start_step and (counter - start_step) % interval == 0.
+ *  - orc_solver_sample_statistics: one sample of the current state with the caller's weight (> 0, finite): for steady runs that
+ *    oscillate, or a schedule of the caller's own.  It does not move the step counter.
+ *  - orc_solver_reset_statistics: accumulators, W and the sample count go to zero; settings and step counter are kept.
+ *  - orc_solver_statistics_info: samples, W, K and the number of boundary faces (0 unless BOUNDARY is on); each pointer may be NULL.
+ *  - orc_solver_get_statistics: the fields of field_mask (OrcStatField bits, ascending) in the cell order of orc_solver_get_fields,
+ *    field k of the selection at out[k * n_cells + c]; the ghost entries of a partitioned mesh are 0.  form RAW: means and weighted
+ *    co-moment sums C; NORMALISED: means and C / W (divided on the host).  RAW with 0 samples returns zeros.
+ *  - orc_solver_set_statistics_state: the restart path.  raw holds exactly the enabled cell fields (field_mask must equal the enabled
+ *    mask) as orc_solver_get_statistics(RAW) returned them; boundary_means holds the 5 * nb doubles of
+ *    orc_solver_get_boundary_statistics when BOUNDARY is on and must be NULL otherwise.  samples == 0 exactly when weight_sum == 0.
+ *    Sampling continues as if the earlier samples had been taken on this solver, bit for bit.
+ *  - orc_solver_get_boundary_statistics: the means of ORC_BOUNDARY_PRESSURE, TRACTION_X, _Y, _Z and SHEAR_MAG of every face of
+ *    orc_mesh_boundary_index, in its order, field k at out[k * nb + i]; needs the BOUNDARY group.  A boundary face in a zone whose type
+ *    the assembly refuses makes this call and orc_solver_set_time_statistics return ORC_ERR_UNSUPPORTED_BC.
+ *  - orc_solver_snapshot / orc_solver_restore do not touch the statistics (as they do not touch the pressure-solver override).
+ *  - On a partitioned mesh every rank enables the same groups and samples at the same steps; nothing is communicated.
+ *  - orc_bench_time_statistics: HIP-event average ms per launch over `reps`: avg_ms[0] the cell pass (time_stats_k of the enabled
+ *    groups, on scratch accumulators), avg_ms[1] the boundary pass (boundary_map_k and stats_mean_k; 0 without BOUNDARY); needs the
+ *    arm on, changes no bit of the solver or its statistics.
+ * All entries but orc_time_statistics_default look for a device first (ORC_ERR_NO_DEVICE without one).  Refused with
+ * ORC_ERR_BAD_ARGUMENT and the solver unchanged: a null solver or output; groups without MEAN or with unknown bits, reserved0 != 0,
+ * interval 0, VISCOSITY without the viscosity arm, SCALAR without the scalar arm; a weight <= 0 or not finite; any entry but the set
+ * call while the arm is off; a field_mask of 0, with unknown bits or with a field whose group is off; an unknown form; NORMALISED
+ * with 0 samples; a state whose mask is not the enabled one, whose weight_sum is negative or not finite, or whose boundary pointer
+ * does not match the BOUNDARY group.  orc_solver_set_scalar(s, NULL) and orc_solver_set_viscosity(s, NULL) are refused the same way
+ * while the SCALAR or VISCOSITY group is on. */
+void orc_time_statistics_default(OrcTimeStatistics *c);
+int orc_solver_set_time_statistics(OrcSolver *s, const OrcTimeStatistics *c /*NULL = off*/);
+int orc_solver_sample_statistics(OrcSolver *s, double weight);
+int orc_solver_reset_statistics(OrcSolver *s);
+int orc_solver_statistics_info(OrcSolver *s, uint64_t *samples, double *weight_sum, int32_t *n_fields, int64_t *n_boundary_faces);
+int orc_solver_get_statistics(OrcSolver *s, uint32_t field_mask, int32_t form, double *out /*[popcount(field_mask) * n_cells]*/);
+int orc_solver_set_statistics_state(OrcSolver *s, uint64_t samples, double weight_sum, uint32_t field_mask,
+                                    const double *raw /*[K * n_cells]*/, const double *boundary_means /*[5 * nb] or NULL*/);
+int orc_solver_get_boundary_statistics(OrcSolver *s, double *out /*[5 * nb]*/);
+int orc_bench_time_statistics(OrcSolver *s, int reps, double avg_ms[2]);
+
 /* ---------- measurement hooks (bench.py): HIP-event timed launches of single kernels ---------- */
 /* y = A x with the momentum matrix a_u of the solver, `reps` launches; returns average ms per launch */
 int orc_bench_spmv(OrcSolver *s, int reps, double *avg_ms, double *checksum);

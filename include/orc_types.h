@@ -318,6 +318,32 @@ typedef struct OrcWallDamping {
     double u_tau;            /* VAN_DRIEST: > 0, the caller's friction velocity (channel: sqrt(h |dp/dx| / rho)); default 0 */
 } OrcWallDamping;            /* 32 bytes */
 
+/* Running time statistics (new-build extension; orc_amd.h: orc_solver_set_time_statistics): weighted running means of the fields and
+ * the weighted co-moment sums C_xy = sum_k w_k (x_k - <x>)(y_k - <y>) of their fluctuations, updated sample by sample with West's
+ * recurrence.  One sample of weight w on the state x:  W' = W + w, r = w / W' (host);  per mean  dx = x - m, m' = m + r * dx,
+ * ex = x - m';  per co-moment of the ordered pair (x, y)  C' = C + (w * dx) * ey.  C / W is the (co)variance.
+ * DESIGN.md §3 "Time statistics" fixes the operator order. */
+enum OrcStatGroup {               /* bits of OrcTimeStatistics::groups */
+    ORC_STAT_GROUP_MEAN = 1,      /* <u> <v> <w> <p>: always required */
+    ORC_STAT_GROUP_STRESS = 2,    /* C_uu C_vv C_ww C_uv C_uw C_vw C_pp */
+    ORC_STAT_GROUP_VISCOSITY = 4, /* <mu>: the cell viscosity the momentum assembly used; needs the viscosity arm */
+    ORC_STAT_GROUP_SCALAR = 8,    /* <phi> C_phiphi C_uphi C_vphi C_wphi; needs the scalar arm */
+    ORC_STAT_GROUP_BOUNDARY = 16  /* per boundary face: <p_f> <t_x> <t_y> <t_z> <shear_mag> (OrcBoundaryField 0..4) */
+};
+/* the cell fields, selected by bit (1 << value) of a mask; a pair XY is ordered: x = the first letter's field, y = the second's */
+enum OrcStatField { ORC_STAT_U = 0, ORC_STAT_V, ORC_STAT_W, ORC_STAT_P,
+                    ORC_STAT_UU, ORC_STAT_VV, ORC_STAT_WW, ORC_STAT_UV, ORC_STAT_UW, ORC_STAT_VW, ORC_STAT_PP,
+                    ORC_STAT_MU, ORC_STAT_PHI, ORC_STAT_PHIPHI, ORC_STAT_UPHI, ORC_STAT_VPHI, ORC_STAT_WPHI,
+                    ORC_STAT_N /* 17 */ };
+enum OrcStatForm { ORC_STAT_RAW = 0 /* means and weighted co-moment sums C */, ORC_STAT_NORMALISED = 1 /* means and C / W */ };
+#define ORC_STAT_BOUNDARY_N 5 /* boundary means per face: ORC_BOUNDARY_PRESSURE .. ORC_BOUNDARY_SHEAR_MAG */
+typedef struct OrcTimeStatistics {
+    uint32_t groups;      /* OrcStatGroup bits; MEAN must be set */
+    int32_t reserved0;    /* 0 */
+    uint64_t start_step;  /* orc_solver_advance samples from this step on (steps counted since the arm was enabled, first = 1) */
+    uint64_t interval;    /* >= 1: every interval-th step from start_step */
+} OrcTimeStatistics;      /* 24 bytes */
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,27 @@ def lib():
             L.orc_solver_set_wall_damping.restype = C.c_int
             L.orc_solver_get_wall_damping.argtypes = [C.c_void_p, C.c_void_p, _i32]
             L.orc_solver_get_wall_damping.restype = C.c_int
+        # running time statistics (orc_amd.h "running time statistics"): full signatures
+        if hasattr(L, "orc_solver_set_time_statistics"):
+            _f64, _u64, _i64, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+            L.orc_time_statistics_default.argtypes = [C.c_void_p]
+            L.orc_time_statistics_default.restype = None
+            L.orc_solver_set_time_statistics.argtypes = [C.c_void_p, C.c_void_p]
+            L.orc_solver_set_time_statistics.restype = C.c_int
+            L.orc_solver_sample_statistics.argtypes = [C.c_void_p, C.c_double]
+            L.orc_solver_sample_statistics.restype = C.c_int
+            L.orc_solver_reset_statistics.argtypes = [C.c_void_p]
+            L.orc_solver_reset_statistics.restype = C.c_int
+            L.orc_solver_statistics_info.argtypes = [C.c_void_p, _u64, _f64, _i32, _i64]
+            L.orc_solver_statistics_info.restype = C.c_int
+            L.orc_solver_get_statistics.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, _f64]
+            L.orc_solver_get_statistics.restype = C.c_int
+            L.orc_solver_set_statistics_state.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_uint32, _f64, _f64]
+            L.orc_solver_set_statistics_state.restype = C.c_int
+            L.orc_solver_get_boundary_statistics.argtypes = [C.c_void_p, _f64]
+            L.orc_solver_get_boundary_statistics.restype = C.c_int
+            L.orc_bench_time_statistics.argtypes = [C.c_void_p, C.c_int, _f64]
+            L.orc_bench_time_statistics.restype = C.c_int
         # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
         if hasattr(L, "orc_debug_amg_setup_stats"):
             L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]

@@ -522,6 +522,7 @@ int advance_one(SolverState &st, double *row /*10*/) {
         if (tol > 0. && (rep[6] < tol * first_vc || rep[6] == 0.) && (rep[7] < tol * first_pc || rep[7] == 0.)) break;
     }
     ORC_TRY(scalar_step_dev(st));  // scalar arm on: its levels shift and it is solved once on this step's flow
+    ORC_TRY(stats_step_dev(st));   // statistics arm on: the step is counted and, when due, sampled with weight dt
     if (row) {
         std::copy(rep, rep + 8, row);
         row[8] = (double)used;

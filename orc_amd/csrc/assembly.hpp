@@ -238,6 +238,20 @@ struct SolverState {
         OrcWallDamping wd{ORC_WALL_DAMPING_NONE, 0, 0.41, 26., 0.};  // wall damping of the Smagorinsky length (orc_solver_set_wall_damping); mode NONE = off
     } vis;
     const double *cell_viscosity() const { return vis.on ? vis.mu.p : nullptr; }  // what the surface reports and boundary maps take
+    // Running time statistics (orc_solver_set_time_statistics, time_stats.hip): off unless enabled, every buffer allocated by the set
+    // call.  Reads the fields, never writes them; snapshot / restore leave it alone.
+    struct TimeStats {
+        bool on = false;
+        OrcTimeStatistics c{};
+        uint32_t field_mask = 0;  // OrcStatField bits of the enabled groups
+        int n_fields = 0;         // K = popcount(field_mask)
+        DevBuf<double> acc;       // [K][n] SoA, enabled fields in enum order, internal cell order; ghost entries stay 0
+        int64_t nb = 0;           // boundary faces (BOUNDARY group), else 0
+        DevBuf<double> bnd, bnd_now;  // [5][nb]: the means, and the maps of the state being sampled
+        DevBuf<int> bnd_status;   // boundary_map_k's status word
+        double W = 0.;            // sum of the weights
+        uint64_t samples = 0, step = 0;  // samples taken; orc_solver_advance steps since the arm was enabled
+    } ts;
 };
 
 int mesh_upload(OrcMesh &m, int64_t n_own, int64_t n_cells, int64_t n_faces, int32_t n_zones, const int64_t *face_c0, const int64_t *face_c1,
@@ -326,6 +340,14 @@ int k_viscosity_update(SolverState &s);
 int wall_distance_default(OrcMesh &m, const double **d_dev);
 void wall_zones_changed(OrcMesh &m, const int32_t *zone_type);
 int wall_damping_validate(const OrcWallDamping &w);  // ORC_ERR_BAD_ARGUMENT with a message, or ORC_OK
+// boundary maps (derived.hip): the fields of `mask` (OrcBoundaryField bits) of device fields in the mesh's internal order into the DEVICE
+// buffer out_dev [popcount(mask)][nb], asynchronous on ctx().stream; a face in a refused zone raises *status_dev.  Builds the boundary
+// index if need be.
+int boundary_maps_dev(OrcMesh &m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
+                      const double *mu_cell, uint32_t mask, double *out_dev, int *status_dev);
+// time statistics (time_stats.hip): what orc_solver_advance runs after scalar_step_dev — counts the step and, when the arm is on and the
+// step is due, takes one sample of weight dt; asynchronous on ctx().stream, nothing while the arm is off
+int stats_step_dev(SolverState &s);
 
 }  // namespace orc
 

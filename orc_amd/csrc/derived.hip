@@ -197,9 +197,7 @@ int boundary_fields_dev(OrcMesh &m, const double *u, const double *v, const doub
     if (nb > 0) {
         DevBuf<double> dev;
         ORC_TRY(dev.alloc((size_t)k * (size_t)nb));
-        BoundaryArgs A{X.bface.p, nb, u, v, w, p, rho, mu, mu_cell, dev.p, mask};
-        hipLaunchKernelGGL(boundary_map_k, dim3(grid_for(nb)), dim3(kBlock), 0, ctx().stream, m.dev(), A, status.p);
-        ORC_HIP(hipGetLastError());
+        ORC_TRY(boundary_maps_dev(m, u, v, w, p, rho, mu, mu_cell, mask, dev.p, status.p));
         ORC_TRY(dev.download(out, (size_t)k * (size_t)nb));
     }
     return fetch(status, m.halo.active(), "boundary fields");
@@ -215,6 +213,18 @@ int upload_in_internal_order(const OrcMesh &m, const double *src, DevBuf<double>
 }
 
 }  // namespace
+
+int boundary_maps_dev(OrcMesh &m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
+                      const double *mu_cell, uint32_t mask, double *out_dev, int *status_dev) {
+    ORC_TRY(surface_index(m));
+    const SurfaceIndex &X = *m.surface;
+    const int64_t nb = X.n_bfaces;
+    if (nb == 0) return ORC_OK;
+    BoundaryArgs A{X.bface.p, nb, u, v, w, p, rho, mu, mu_cell, out_dev, mask};
+    hipLaunchKernelGGL(boundary_map_k, dim3(grid_for(nb)), dim3(kBlock), 0, ctx().stream, m.dev(), A, status_dev);
+    ORC_HIP(hipGetLastError());
+    return ORC_OK;
+}
 
 }  // namespace orc
 

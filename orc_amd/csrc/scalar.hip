@@ -465,6 +465,8 @@ int orc_solver_set_scalar(OrcSolver *s, const OrcScalarSettings *cfg_in) {
     if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
     SolverState &st = s->st;
     if (!cfg_in) {
+        if (st.ts.on && (st.ts.c.groups & ORC_STAT_GROUP_SCALAR))
+            return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: the time statistics' SCALAR group is on (orc_solver_set_time_statistics)");
         st.sc = SolverState::Scalar();
         return ORC_OK;
     }

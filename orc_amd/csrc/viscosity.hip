@@ -293,6 +293,8 @@ int orc_solver_set_viscosity(OrcSolver *s, const OrcViscosity *c) {
     SolverState &st = s->st;
     SolverState::Viscosity &V = st.vis;
     if (!c) {  // back to the constant mu: k_diffusion's a_di and wall terms, nothing of the arm is launched from here on
+        if (st.ts.on && (st.ts.c.groups & ORC_STAT_GROUP_VISCOSITY))
+            return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: the time statistics' VISCOSITY group is on (orc_solver_set_time_statistics)");
         const bool was_on = V.on;
         ORC_HIP(hipStreamSynchronize(ctx().stream));
         const OrcWallDamping wd = V.wd;  // the damping setting is the solver's, not the arm's: it waits for the next SMAGORINSKY

@@ -175,3 +175,29 @@ class WallDamping(C.Structure):
                 raise AttributeError(k)
             setattr(s, k, v)
         return s
+
+
+class StatGroup:  # include/orc_types.h OrcStatGroup (bits)
+    MEAN, STRESS, VISCOSITY, SCALAR, BOUNDARY = 1, 2, 4, 8, 16
+    ALL = 31
+
+
+class StatForm:  # include/orc_types.h OrcStatForm
+    RAW, NORMALISED = 0, 1
+
+
+class TimeStatistics(C.Structure):
+    """OrcTimeStatistics: running time means and co-moments of the fields (Solver.set_time_statistics) — `groups` is a sum of StatGroup
+    bits (MEAN always); Solver.advance samples every `interval`-th step from `start_step` on (steps counted from 1 since the arm was
+    enabled) with weight dt."""
+    _fields_ = [("groups", C.c_uint32), ("reserved0", C.c_int32), ("start_step", C.c_uint64), ("interval", C.c_uint64)]
+
+    @classmethod
+    def make(cls, groups=None, start_step=1, interval=1):
+        """orc_time_statistics_default (MEAN | STRESS, every step from the first) with the groups, start_step and interval overridden"""
+        s = cls()
+        lib().orc_time_statistics_default(C.byref(s))
+        if groups is not None:
+            s.groups = int(groups)
+        s.start_step, s.interval = int(start_step), int(interval)
+        return s

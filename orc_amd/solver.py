@@ -257,6 +257,12 @@ def boundary_fields(mesh, u, v, w, p, rho, mu, names=BOUNDARY_NAMES, raise_on_er
     return st, (_boundary_result(mesh, out, mask, names) if st == 0 else None)
 
 
+# orc_types.h OrcStatField, by value: running means of the fields and co-moments of their fluctuations (Solver.statistics)
+STATISTIC_NAMES = ("u", "v", "w", "p", "uu", "vv", "ww", "uv", "uw", "vw", "pp", "mu", "phi", "phiphi", "uphi", "vphi", "wphi")
+STAT_BOUNDARY_NAMES = BOUNDARY_NAMES[:5]  # the boundary maps whose running means the BOUNDARY group keeps
+_STAT_MEAN, _STAT_STRESS, _STAT_SCALAR = STATISTIC_NAMES[:4], STATISTIC_NAMES[4:11], STATISTIC_NAMES[12:]
+
+
 class Solver:
     """Device-resident state of one solve_steady call (OrcSolver*): what bench.py drives."""
 
@@ -267,6 +273,8 @@ class Solver:
         check(st.value)
         self.ptr = C.c_void_p(self.ptr)
         self.n = mesh.n_cells
+        self.rho, self.mu = float(rho), float(mu)
+        self._stat_groups = 0
 
     def __del__(self):
         if getattr(self, "ptr", None):
@@ -509,6 +517,113 @@ class Solver:
         """orc_bench_viscosity: (ms per law pass viscosity_cell_k, ms per rebuild diffusion_var_k); needs set_viscosity()"""
         ms = np.zeros(2)
         check(lib().orc_bench_viscosity(self.ptr, C.c_int(reps), _p(ms)))
+        return float(ms[0]), float(ms[1])
+
+    # ---------------------------------------------------------------- running time statistics (orc_solver_set_time_statistics)
+    def set_time_statistics(self, c=None, raise_on_error=True):
+        """a settings.TimeStatistics turns the statistics arm on (zeroed accumulators, no samples, step counter 0): from then on
+        advance() samples the steps that are due with weight dt; None turns it off and frees its buffers.  Reads only: fields and
+        reports keep their bits.  On a partitioned mesh every rank enables the same groups."""
+        st = lib().orc_solver_set_time_statistics(self.ptr, C.byref(c) if c is not None else None)
+        if st == 0:
+            self._stat_groups = int(c.groups) if c is not None else 0  # OrcStatGroup bits in force
+        if raise_on_error:
+            check(st)
+        return st
+
+    def sample_statistics(self, weight=1.0, raise_on_error=True):
+        """one sample of the current state with `weight` (> 0): for steady runs that oscillate, or a schedule of the caller's own"""
+        st = lib().orc_solver_sample_statistics(self.ptr, C.c_double(weight))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def reset_statistics(self, raise_on_error=True):
+        """accumulators, weight sum and sample count back to zero; the settings and the step counter are kept"""
+        st = lib().orc_solver_reset_statistics(self.ptr)
+        if raise_on_error:
+            check(st)
+        return st
+
+    def statistics_info(self, raise_on_error=True):
+        """dict(samples, weight_sum, n_fields, n_boundary_faces) (raise_on_error=False: (status, dict))"""
+        ns, w, k, nb = C.c_uint64(0), C.c_double(0.0), C.c_int32(0), C.c_int64(0)
+        st = lib().orc_solver_statistics_info(self.ptr, C.byref(ns), C.byref(w), C.byref(k), C.byref(nb))
+        info = dict(samples=int(ns.value), weight_sum=w.value, n_fields=k.value, n_boundary_faces=int(nb.value))
+        if raise_on_error:
+            check(st)
+            return info
+        return st, info
+
+    def statistics_fields(self):
+        """the names (STATISTIC_NAMES) of the enabled cell fields, in the order of the accumulator buffer"""
+        g = self._stat_groups
+        return [n for n in STATISTIC_NAMES if n in _STAT_MEAN or (n in _STAT_STRESS and g & 2) or (n == "mu" and g & 4) or (n in _STAT_SCALAR and g & 8)]
+
+    def statistics(self, names=None, normalised=True, raise_on_error=True):
+        """orc_solver_get_statistics: {name: ndarray[n]} of the statistics `names` (STATISTIC_NAMES or a bit mask; None = every enabled
+        field), cell order as get_fields() — the means, and the co-moments divided by the weight sum (normalised=False: the weighted
+        co-moment sums themselves).  The dict serves as cell data of io.write_vtu.  (raise_on_error=False: (status, dict))"""
+        if names is None:
+            names = self.statistics_fields()
+        mask, names = _mask_of(names, STATISTIC_NAMES)
+        out = np.zeros((max(bin(mask).count("1"), 1), self.n))
+        st = lib().orc_solver_get_statistics(self.ptr, C.c_uint32(mask & 0xFFFFFFFF), C.c_int32(1 if normalised else 0), _p(out))
+        rows = {STATISTIC_NAMES[k]: out[i] for i, k in enumerate(k for k in range(len(STATISTIC_NAMES)) if mask >> k & 1)}
+        if raise_on_error:
+            check(st)
+            return {name: rows[name] for name in names}
+        return st, ({name: rows[name] for name in names} if st == 0 else {})
+
+    def boundary_statistics(self, raise_on_error=True):
+        """orc_solver_get_boundary_statistics: the running means of the boundary maps STAT_BOUNDARY_NAMES -> BoundaryFields (its
+        zone_ptr and faces are Mesh.boundary_index()'s); needs the BOUNDARY group (raise_on_error=False: (status, BoundaryFields or None))"""
+        nb = int(self.mesh.boundary_index()[0][-1])
+        out = np.zeros((len(STAT_BOUNDARY_NAMES), max(nb, 1)))[:, :nb]
+        out = np.ascontiguousarray(out)
+        st = lib().orc_solver_get_boundary_statistics(self.ptr, _p(out))
+        if raise_on_error:
+            check(st)
+        res = _boundary_result(self.mesh, out, (1 << len(STAT_BOUNDARY_NAMES)) - 1, list(STAT_BOUNDARY_NAMES)) if st == 0 else None
+        return res if raise_on_error else (st, res)
+
+    def statistics_state(self):
+        """what a restart needs: dict(samples, weight_sum, names, raw (K, n): every enabled field, RAW form, boundary (5, nb) or None)"""
+        info = self.statistics_info()
+        names = self.statistics_fields()
+        raw = self.statistics(names, normalised=False)
+        state = dict(samples=info["samples"], weight_sum=info["weight_sum"], names=names, raw=np.stack([raw[n] for n in names]), boundary=None)
+        if info["n_boundary_faces"] > 0:
+            b = self.boundary_statistics()
+            state["boundary"] = np.stack([b[n] for n in STAT_BOUNDARY_NAMES])
+        return state
+
+    def set_statistics_state(self, state, raise_on_error=True):
+        """orc_solver_set_statistics_state: continue from a statistics_state() (of this or another solver with the same groups enabled)"""
+        mask, _ = _mask_of(list(state["names"]), STATISTIC_NAMES)
+        raw = _f64(state["raw"])
+        assert raw.size == len(state["names"]) * self.n
+        b = None if state.get("boundary") is None else _f64(state["boundary"])
+        st = lib().orc_solver_set_statistics_state(self.ptr, C.c_uint64(state["samples"]), C.c_double(state["weight_sum"]),
+                                                   C.c_uint32(mask), _p(raw), None if b is None else _p(b))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def mean_friction_velocity(self, zone_name):
+        """sqrt((sum_f A <shear_mag> / sum_f A) / rho) over the boundary faces of the zone `zone_name` (a name or an index): the friction
+        velocity of the time-mean wall shear, the number settings.WallDamping.u_tau asks for.  Host arithmetic on boundary_statistics()."""
+        b = self.boundary_statistics()
+        if isinstance(zone_name, str):
+            zone_name = list(self.mesh.arrays["zone_names"]).index(zone_name)
+        lo, hi = int(b.zone_ptr[zone_name]), int(b.zone_ptr[zone_name + 1])
+        area = np.asarray(self.mesh.arrays["face_area"])[np.asarray(b.faces[lo:hi])]
+        return float(np.sqrt((np.sum(area * b["shear_mag"][lo:hi]) / np.sum(area)) / self.rho))
+
+    def bench_time_statistics(self, reps=50):
+        """orc_bench_time_statistics: (ms per cell pass time_stats_k, ms per boundary pass); needs set_time_statistics()"""
+        ms = np.zeros(2)
+        check(lib().orc_bench_time_statistics(self.ptr, C.c_int(reps), _p(ms)))
         return float(ms[0]), float(ms[1])
 
     def surface_report(self, origin=None, raise_on_error=True):
