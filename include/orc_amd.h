@@ -610,6 +610,52 @@ int orc_solver_set_statistics_state(OrcSolver *s, uint64_t samples, double weigh
 int orc_solver_get_boundary_statistics(OrcSolver *s, double *out /*[5 * nb]*/);
 int orc_bench_time_statistics(OrcSolver *s, int reps, double avg_ms[2]);
 
+/* ---------- point probes (new-build extension, orc_types.h OrcProbeStatus / OrcProbeField / OrcProbeInterpolation) ----------
+ * A probe set is a list of points located in the cells of one mesh: per point the owned cell with the nearest centroid, then a walk
+ * across faces to a cell that contains the point (orc_types.h, DESIGN.md §3 "Point probes": operator order and tie rules).  The set
+ * lives on the device; a solver of the same mesh samples its fields there, at any time or step by step into a history.  Opt-in and
+ * read-only: no entry changes a bit of a mesh or a solver, and a solver without a probe history launches what it launched before.
+ *  - orc_probes_create: locates all n_points points xyz (point-major) at once; NULL + *status on failure.  A partitioned mesh is
+ *    refused (a rank-confined walk leaves points unclaimed).  Destroy a probe set before its mesh.
+ *  - orc_probes_get: per point the cell (ORC order, as orc_mesh_cell_order), the OrcProbeStatus, the moves of the walk, the zone of the
+ *    boundary face an OUTSIDE point left through (-1 otherwise) and the excess, the largest g of the final cell (<= 0 exactly when
+ *    INSIDE).  Each output may be NULL.
+ *  - orc_solver_sample_probes: the fields of field_mask (OrcProbeField bits, ascending) at the points, field k at out[k * n_points + i].
+ *    OUTSIDE and WALK_LIMIT points are sampled at their final cell.  LINEAR evaluates the cell's gradient for the hit cells only, by the
+ *    assembly's per-cell bodies; a zone type the assembly refuses returns ORC_ERR_UNSUPPORTED_BC, a singular least-squares system
+ *    ORC_ERR_SINGULAR_MATRIX, as orc_solver_derived_fields.
+ *  - orc_solver_set_probe_history: p == NULL turns the history off and drops it; otherwise from now on orc_solver_advance appends one
+ *    record after every step whose counter (steps since enabling, first = 1) is a multiple of `interval`: the time reached (slot 9 of
+ *    the step's report) and popcount(field_mask) * n_points values laid out as by orc_solver_sample_probes.  The record is sampled on
+ *    the device after the step's statistics and copied asynchronously: no synchronisation is added to a step.
+ *  - orc_solver_record_probes: appends one record of the current state with `tag` in the time slot (steady runs).
+ *  - orc_solver_probe_history_count / orc_solver_probe_history: the records [first, first + count); times[count],
+ *    out[count][popcount][n_points]; each may be NULL.  orc_solver_snapshot / orc_solver_restore leave the history alone.
+ *  - orc_debug_probes_locate: orc_probes_create with cull = 0 (every cell for every point) or a forced number of cell slabs (0 = the
+ *    library's choice); the result does not depend on either.
+ *  - orc_debug_probe_search: out = {cell tile length T, cell tiles of the last search, tile visits summed over waves, waves, slabs of
+ *    the last search, walk moves summed over points}, the sums since the last reset.
+ *  - orc_bench_probe_locate: HIP-event average ms over `reps` of avg_ms[0] the search and its fold, avg_ms[1] the walk, of the points
+ *    of `p` on scratch buffers.
+ * Every entry looks for a device first (ORC_ERR_NO_DEVICE without one).  Refused with ORC_ERR_BAD_ARGUMENT, solver and mesh unchanged:
+ * a null mesh, solver, probe set or coordinate array; n_points < 1; a coordinate that is not finite; a partitioned mesh; a field_mask
+ * of 0 or with unknown bits; ORC_PROBE_PHI without the scalar arm; an unknown interpolation; interval 0; a probe set of another mesh;
+ * orc_solver_record_probes and orc_solver_probe_history while the history is off; a range past the history. */
+typedef struct OrcProbes OrcProbes;
+OrcProbes *orc_probes_create(OrcMesh *m, int64_t n_points, const double *xyz /*[3 * n_points] point-major*/, int *status);
+void orc_probes_destroy(OrcProbes *p);
+int64_t orc_probes_count(const OrcProbes *p);
+int orc_probes_get(const OrcProbes *p, int64_t *cell, int32_t *status, int32_t *steps, int32_t *zone, double *excess /*[n_points] each, or NULL*/);
+int orc_solver_sample_probes(OrcSolver *s, const OrcProbes *p, uint32_t field_mask, int32_t interpolation,
+                             double *out /*[popcount(field_mask) * n_points]*/);
+int orc_solver_set_probe_history(OrcSolver *s, const OrcProbes *p /*NULL = off*/, uint32_t field_mask, int32_t interpolation, uint64_t interval);
+int orc_solver_record_probes(OrcSolver *s, double tag);
+int64_t orc_solver_probe_history_count(OrcSolver *s);
+int orc_solver_probe_history(OrcSolver *s, uint64_t first, uint64_t count, double *times /*[count]*/, double *out /*[count * popcount * n_points]*/);
+OrcProbes *orc_debug_probes_locate(OrcMesh *m, int64_t n_points, const double *xyz, int cull, int slabs /*0 = automatic*/, int *status);
+int orc_debug_probe_search(long long out[6], int reset);
+int orc_bench_probe_locate(OrcMesh *m, const OrcProbes *p, int cull, int reps, double avg_ms[2]);
+
 /* ---------- measurement hooks (bench.py): HIP-event timed launches of single kernels ---------- */
 /* y = A x with the momentum matrix a_u of the solver, `reps` launches; returns average ms per launch */
 int orc_bench_spmv(OrcSolver *s, int reps, double *avg_ms, double *checksum);

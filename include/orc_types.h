@@ -344,6 +344,29 @@ typedef struct OrcTimeStatistics {
     uint64_t interval;    /* >= 1: every interval-th step from start_step */
 } OrcTimeStatistics;      /* 24 bytes */
 
+/* Point probes (new-build extension; orc_amd.h: orc_probes_create, orc_solver_sample_probes): a point is located by the owned cell with
+ * the nearest centroid (smallest s = (r.x r.x + r.y r.y) + r.z r.z, r = x - x_P; the smallest ORC cell id among exact ties) followed by
+ * a walk: at cell P the face f of its face list with the largest g_f = (r.x n.x + r.y n.y) + r.z n.z, r = x - x_f, the sign turned
+ * where P is not the face's first cell (the first face among exact ties), decides — g <= 0: INSIDE P; a boundary face: OUTSIDE, left
+ * through that face's zone; else on to the cell across, at most ORC_PROBE_WALK_LIMIT times.  DESIGN.md §3 "Point probes" fixes the
+ * operator order. */
+enum OrcProbeStatus {
+    ORC_PROBE_STATUS_INSIDE = 0,     /* every face of the cell has g <= 0 */
+    ORC_PROBE_STATUS_OUTSIDE = 1,    /* the walk left the mesh through a boundary face of the cell */
+    ORC_PROBE_STATUS_WALK_LIMIT = 2  /* ORC_PROBE_WALK_LIMIT moves made and the cell reached still has an interior face with g > 0 */
+};
+#define ORC_PROBE_WALK_LIMIT 64 /* moves of a walk */
+/* the sampled fields, selected by bit (1 << value) of a mask */
+enum OrcProbeField { ORC_PROBE_U = 0, ORC_PROBE_V, ORC_PROBE_W, ORC_PROBE_P,
+                     ORC_PROBE_PHI, /* the scalar arm's field; needs the arm */
+                     ORC_PROBE_MU,  /* the viscosity the last assembly used (the constant while the viscosity arm is off) */
+                     ORC_PROBE_N /* 6 */ };
+enum OrcProbeInterpolation {
+    ORC_PROBE_CELL = 0,  /* the value of the cell */
+    ORC_PROBE_LINEAR = 1 /* u, v, w, p: phi_P + ((G.x r.x + G.y r.y) + G.z r.z), G the cell's gradient of the solver's
+                            gradient_reconstruction (a row of orc_calculate_gradients, bit for bit), r = x - x_P; PHI and MU: the cell's */
+};
+
 #ifdef __cplusplus
 }
 #endif

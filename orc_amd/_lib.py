@@ -152,6 +152,33 @@ def lib():
             L.orc_solver_get_boundary_statistics.restype = C.c_int
             L.orc_bench_time_statistics.argtypes = [C.c_void_p, C.c_int, _f64]
             L.orc_bench_time_statistics.restype = C.c_int
+        # point probes (orc_amd.h "point probes"): full signatures
+        if hasattr(L, "orc_probes_create"):
+            _f64, _i64, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+            L.orc_probes_create.argtypes = [C.c_void_p, C.c_int64, _f64, C.POINTER(C.c_int)]
+            L.orc_probes_create.restype = C.c_void_p
+            L.orc_debug_probes_locate.argtypes = [C.c_void_p, C.c_int64, _f64, C.c_int, C.c_int, C.POINTER(C.c_int)]
+            L.orc_debug_probes_locate.restype = C.c_void_p
+            L.orc_probes_destroy.argtypes = [C.c_void_p]
+            L.orc_probes_destroy.restype = None
+            L.orc_probes_count.argtypes = [C.c_void_p]
+            L.orc_probes_count.restype = C.c_int64
+            L.orc_probes_get.argtypes = [C.c_void_p, _i64, _i32, _i32, _i32, _f64]
+            L.orc_probes_get.restype = C.c_int
+            L.orc_solver_sample_probes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, _f64]
+            L.orc_solver_sample_probes.restype = C.c_int
+            L.orc_solver_set_probe_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_uint64]
+            L.orc_solver_set_probe_history.restype = C.c_int
+            L.orc_solver_record_probes.argtypes = [C.c_void_p, C.c_double]
+            L.orc_solver_record_probes.restype = C.c_int
+            L.orc_solver_probe_history_count.argtypes = [C.c_void_p]
+            L.orc_solver_probe_history_count.restype = C.c_int64
+            L.orc_solver_probe_history.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, _f64, _f64]
+            L.orc_solver_probe_history.restype = C.c_int
+            L.orc_debug_probe_search.argtypes = [C.POINTER(C.c_longlong), C.c_int]
+            L.orc_debug_probe_search.restype = C.c_int
+            L.orc_bench_probe_locate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _f64]
+            L.orc_bench_probe_locate.restype = C.c_int
         # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
         if hasattr(L, "orc_debug_amg_setup_stats"):
             L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]

@@ -67,30 +67,14 @@ __global__ void extract_diag_k(SellDev P, const double *__restrict__ a, double *
 }
 
 // ------------------------------------------------------------------ K9: Green-Gauss gradients
-// get_face_pressure with PressureInterpolation::Linear (solver.rs:1114-1128)
-__device__ __forceinline__ double face_pressure_linear(const MeshDev &M, const double *__restrict__ p, int f, int zt, int z) {
-    if (zt == ORC_BC_INTERIOR) return (p[M.c0[f]] + p[M.c1[f]]) * 0.5;
-    if (zt == ORC_BC_PRESSURE_INLET || zt == ORC_BC_PRESSURE_OUTLET) return M.zscal[z];
-    return p[M.c0[f]];  // Symmetry | Wall | VelocityInlet
-}
+// face_pressure_linear — get_face_pressure with PressureInterpolation::Linear — lives in gradient_cell.hpp beside the gradient bodies.
 
-
-// calculate_pressure_gradient, GreenGauss(CellBased) (solver.rs:883-900); returns (gx, gy, gy) under Q1
+// calculate_pressure_gradient, GreenGauss(CellBased) (solver.rs:883-900); returns (gx, gy, gy) under Q1; the per-cell body is
+// grad_p_gg_cell (gradient_cell.hpp), shared with probe_sample_k
 __global__ void grad_p_k(MeshDev M, const double *__restrict__ p, double *__restrict__ gp, int q1, int *status) {
     const int64_t n = M.n_cells;
     GRID_STRIDE(c, M.n_own) {
-        const double vol = M.vol[c];
-        V3 acc = mk(0., 0., 0.);
-        for (int q = M.cfp[c]; q < M.cfp[c + 1]; ++q) {
-            const int f = M.cf[q];
-            const int z = M.fzone[f];
-            const int zt = M.ztype[z];
-            if (!bc_supported(zt)) { raise(status, ORC_ERR_UNSUPPORTED_BC); continue; }  // solver.rs:1148
-            const double fv = face_pressure_linear(M, p, f, zt, z);
-            V3 nrm = face_normal(M, f);
-            if (M.c0[f] != c) nrm = vneg(nrm);
-            acc = vadd(acc, smulv(fv * (M.area[f] / vol), nrm, q1));  // :896-898
-        }
+        const V3 acc = grad_p_gg_cell(M, p, c, q1, status);
         gp[c] = acc.x; gp[n + c] = acc.y; gp[2 * n + c] = acc.z;
     }
 }
@@ -115,29 +99,8 @@ __global__ void grad_u_k(MeshDev M, const double *__restrict__ u, const double *
 __global__ void grad_p_lsq_k(MeshDev M, const double *__restrict__ p, double *__restrict__ gp, int *status) {
     const int64_t n = M.n_cells;
     GRID_STRIDE(c, M.n_own) {
-        const V3 cc = cell_centroid(M, (int)c);
-        Lsq3 L;
-        for (int q = M.cfp[c]; q < M.cfp[c + 1]; ++q) {
-            const int f = M.cf[q];
-            const int z = M.fzone[f];
-            const int zt = M.ztype[z];
-            if (!bc_supported(zt)) { raise(status, ORC_ERR_UNSUPPORTED_BC); continue; }
-            V3 d;
-            double val;
-            if (zt == ORC_BC_INTERIOR) {
-                const int nb = (M.c0[f] == c) ? M.c1[f] : M.c0[f];
-                d = vsub(cell_centroid(M, nb), cc);
-                val = p[nb] - p[c];
-            } else {  // get_face_pressure(…, None, None): zone scalar on pressure zones, cell-0 value elsewhere
-                d = vsub(face_centroid(M, f), cc);
-                val = (zt == ORC_BC_PRESSURE_INLET || zt == ORC_BC_PRESSURE_OUTLET) ? M.zscal[z] : p[M.c0[f]];
-            }
-            const double x[3] = {d.x, d.y, d.z};
-            L.add_row(x, &val, 1);
-        }
-        double g[3] = {0., 0., 0.};
-        if (L.first || !inverse3(L.ata)) raise(status, ORC_ERR_SINGULAR_MATRIX);  // a cell without faces: 0 x 0 ... the reference cannot get there either
-        else inv_times3(L.ata, L.atb[0], g);
+        double g[3];
+        grad_p_lsq_cell(M, p, c, status, g);  // gradient_cell.hpp, shared with probe_sample_k
         gp[c] = g[0]; gp[n + c] = g[1]; gp[2 * n + c] = g[2];
     }
 }

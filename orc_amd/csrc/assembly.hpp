@@ -52,6 +52,15 @@ struct WallDistance {
     bool searched = false;       // d holds the field
 };
 
+// What the point search of probes.hip keeps per mesh, built at the first orc_probes_create: tile t covers the owned cells
+// [t * kProbeTile, (t + 1) * kProbeTile) of the internal numbering and carries a bounding sphere of their centroids; the cell geometry
+// of a mesh never changes, so the spheres live as long as the mesh.
+struct ProbeTiles {
+    int64_t n_tiles = 0;
+    DevBuf<double> tiles;     // [4][n_tiles]: sphere centre x, y, z and (widened) radius
+    DevBuf<int32_t> orc_id;   // [n_cells] ORC id of every internal cell; empty when the numbering is ORC's own
+};
+
 #ifdef __HIPCC__
 // the TVD limiters of settings::MomentumDiscretization (lib.rs:107-118): momentum_k and the scalar arm's scalar_face_k
 __device__ __forceinline__ double psi_eval(int momentum, double r) {
@@ -88,6 +97,7 @@ struct OrcMesh {
                                             // orc_solver_set_fields / get_fields / orc_solve_steady permute through it
     std::unique_ptr<orc::SurfaceIndex> surface;  // null until the first surface report (surface.hip)
     std::unique_ptr<orc::WallDistance> wall;     // null until the first wall distance (wall_distance.hip)
+    std::unique_ptr<orc::ProbeTiles> probe_tiles;  // null until the first probe set (probes.hip)
     orc::MeshDev dev() const;
 };
 
@@ -252,6 +262,37 @@ struct SolverState {
         double W = 0.;            // sum of the weights
         uint64_t samples = 0, step = 0;  // samples taken; orc_solver_advance steps since the arm was enabled
     } ts;
+    // Probe history (orc_solver_set_probe_history, probes.hip): off unless enabled.  A record is sampled on the device into `rec`,
+    // copied to the pinned `raw` behind it and marked by `copied`; it joins the history at the next step, at a history call or when the
+    // arm goes off — by then the step's last synchronisation has long completed the copy.  Reads the fields, never writes them;
+    // snapshot / restore leave it alone.
+    struct ProbeHistory {
+        bool on = false;
+        const OrcProbes *probes = nullptr;
+        uint32_t mask = 0;
+        int32_t interpolation = 0;
+        int n_fields = 0;
+        uint64_t interval = 1, step = 0;  // orc_solver_advance steps since the arm was enabled
+        DevBuf<double> rec;               // [n_fields][n_points], the points in the probe set's device order
+        DevBuf<int> status;               // probe_sample_k's status word
+        double *raw = nullptr;            // [n_fields * n_points + 1] pinned: the record, then the status word as a double
+        hipEvent_t copied = nullptr;
+        bool pending = false;             // raw is on its way
+        double pending_time = 0.;
+        std::vector<double> times, values;  // k records: the time slots, and k * n_fields * n_points values in the caller's point order
+        ProbeHistory() = default;
+        ProbeHistory(const ProbeHistory &) = delete;
+        ProbeHistory &operator=(const ProbeHistory &) = delete;
+        ~ProbeHistory() { clear(); }
+        void clear() {
+            if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
+            if (raw) (void)hipHostFree(raw);
+            copied = nullptr; raw = nullptr;
+            rec.release(); status.release();
+            on = false; pending = false; probes = nullptr; mask = 0; n_fields = 0; step = 0;
+            times.clear(); values.clear();
+        }
+    } ph;
 };
 
 int mesh_upload(OrcMesh &m, int64_t n_own, int64_t n_cells, int64_t n_faces, int32_t n_zones, const int64_t *face_c0, const int64_t *face_c1,
@@ -348,6 +389,9 @@ int boundary_maps_dev(OrcMesh &m, const double *u, const double *v, const double
 // time statistics (time_stats.hip): what orc_solver_advance runs after scalar_step_dev — counts the step and, when the arm is on and the
 // step is due, takes one sample of weight dt; asynchronous on ctx().stream, nothing while the arm is off
 int stats_step_dev(SolverState &s);
+// probe history (probes.hip): what orc_solver_advance runs after stats_step_dev — counts the step and, when the history is on and the
+// step is due, samples one record on the device and starts its copy to the host; asynchronous on ctx().stream, nothing while it is off
+int probes_step_dev(SolverState &s);
 
 }  // namespace orc
 

@@ -1,7 +1,7 @@
-// gradient_cell.hpp — the per-cell velocity-gradient arithmetic of the assembly (K9), shared by grad_u_k / grad_u_lsq_k
-// (assembly.hip), derived_cell_k (derived.hip) and viscosity_cell_k (viscosity.hip): the small vector type, the boundary-value rules, the
-// two per-cell bodies and the strain-rate magnitude the last two form from them; the grid-stride loop of the assembly kernels
-// (assembly.hip, initialize.hip).
+// gradient_cell.hpp — the per-cell gradient arithmetic of the assembly (K9), shared by grad_u_k / grad_u_lsq_k / grad_p_k / grad_p_lsq_k
+// (assembly.hip), derived_cell_k (derived.hip), viscosity_cell_k (viscosity.hip) and probe_sample_k (probes.hip): the small vector type,
+// the boundary-value rules, the two per-cell bodies of the velocity gradient and the two of the pressure gradient, the strain-rate
+// magnitude; the grid-stride loop of the assembly kernels (assembly.hip, initialize.hip).
 // Device code only.  Every operation and its order are the reference's; a kernel that calls a body gets the same bits as any other.
 #pragma once
 #include "assembly.hpp"
@@ -175,6 +175,59 @@ __device__ __forceinline__ void grad_u_lsq_cell(const MeshDev &M, const double *
         inv_times3(L.ata, L.atb[1], g[1]);
         inv_times3(L.ata, L.atb[2], g[2]);
     }
+}
+
+// get_face_pressure with PressureInterpolation::Linear (solver.rs:1114-1128)
+__device__ __forceinline__ double face_pressure_linear(const MeshDev &M, const double *__restrict__ p, int f, int zt, int z) {
+    if (zt == ORC_BC_INTERIOR) return (p[M.c0[f]] + p[M.c1[f]]) * 0.5;
+    if (zt == ORC_BC_PRESSURE_INLET || zt == ORC_BC_PRESSURE_OUTLET) return M.zscal[z];
+    return p[M.c0[f]];  // Symmetry | Wall | VelocityInlet
+}
+
+// The Green-Gauss pressure gradient of cell c (calculate_pressure_gradient, GreenGauss(CellBased), solver.rs:883-900): the body of
+// grad_p_k (assembly.hip), shared with probe_sample_k (probes.hip); returns (gx, gy, gy) under Q1
+__device__ __forceinline__ V3 grad_p_gg_cell(const MeshDev &M, const double *__restrict__ p, int64_t c, int q1, int *status) {
+    const double vol = M.vol[c];
+    V3 acc = mk(0., 0., 0.);
+    for (int q = M.cfp[c]; q < M.cfp[c + 1]; ++q) {
+        const int f = M.cf[q];
+        const int z = M.fzone[f];
+        const int zt = M.ztype[z];
+        if (!bc_supported(zt)) { raise(status, ORC_ERR_UNSUPPORTED_BC); continue; }  // solver.rs:1148
+        const double fv = face_pressure_linear(M, p, f, zt, z);
+        V3 nrm = face_normal(M, f);
+        if (M.c0[f] != c) nrm = vneg(nrm);
+        acc = vadd(acc, smulv(fv * (M.area[f] / vol), nrm, q1));  // :896-898
+    }
+    return acc;
+}
+
+// The least-squares pressure gradient of cell c: the body of grad_p_lsq_k (assembly.hip), rows as in grad_u_lsq_cell; zeros and
+// ORC_ERR_SINGULAR_MATRIX when the normal matrix has no inverse
+__device__ __forceinline__ void grad_p_lsq_cell(const MeshDev &M, const double *__restrict__ p, int64_t c, int *status, double g[3]) {
+    const V3 cc = cell_centroid(M, (int)c);
+    Lsq3 L;
+    for (int q = M.cfp[c]; q < M.cfp[c + 1]; ++q) {
+        const int f = M.cf[q];
+        const int z = M.fzone[f];
+        const int zt = M.ztype[z];
+        if (!bc_supported(zt)) { raise(status, ORC_ERR_UNSUPPORTED_BC); continue; }
+        V3 d;
+        double val;
+        if (zt == ORC_BC_INTERIOR) {
+            const int nb = (M.c0[f] == c) ? M.c1[f] : M.c0[f];
+            d = vsub(cell_centroid(M, nb), cc);
+            val = p[nb] - p[c];
+        } else {  // get_face_pressure(…, None, None): zone scalar on pressure zones, cell-0 value elsewhere
+            d = vsub(face_centroid(M, f), cc);
+            val = (zt == ORC_BC_PRESSURE_INLET || zt == ORC_BC_PRESSURE_OUTLET) ? M.zscal[z] : p[M.c0[f]];
+        }
+        const double x[3] = {d.x, d.y, d.z};
+        L.add_row(x, &val, 1);
+    }
+    g[0] = 0.; g[1] = 0.; g[2] = 0.;
+    if (L.first || !inverse3(L.ata)) raise(status, ORC_ERR_SINGULAR_MATRIX);  // a cell without faces: 0 x 0 ... the reference cannot get there either
+    else inv_times3(L.ata, L.atb[0], g);
 }
 
 // SS = S : S of the gradient rows gx, gy, gz (G[i][j] = row i, component j) and the strain-rate magnitude sqrt(2 SS), in THE operator

@@ -11,7 +11,7 @@
 //     (host)          exclusive scan of the segment counts
 //     wall_place_k    the same walk: the wall faces, ascending in face id, into the SoA table [6][W] at this rank's offset
 //     (partitioned)   the per-rank counts, then the zero-filled table with every rank's slice, summed over the ranks: x + 0 is exact
-//     wall_tiles_k    one thread per tile of kWallTile consecutive entries: a sphere around the tile's centroids, radius widened
+//     sphere_tiles_k  (sphere_cull.hpp) one thread per tile of kWallTile consecutive entries: a sphere around the tile's centroids
 //   the search (one launch, fp64, compute-bound: N W pairs un-culled)
 //     wall_search_k   one lane per owned cell; the wave walks the table, whose entry is wave-uniform and arrives through scalar loads.
 //                     Culled (the default): the tile whose centre is nearest to the wave's first cell seeds the best value, then a
@@ -23,16 +23,14 @@
 #include <initializer_list>
 
 #include "assembly.hpp"
+#include "sphere_cull.hpp"
 
 namespace orc {
 
-constexpr int kWallTile = 64;       // table entries per tile: one bounding sphere, one skip decision per wave
+constexpr int kWallTile = 64;      // table entries per tile: one bounding sphere, one skip decision per wave
 constexpr int kWallSegment = 256;   // consecutive faces one thread of the table build walks
 
 namespace {
-
-// the safety factors of the skip: every rounding of the bound is below 2^-50 relative, the factors move it by 2^-40
-constexpr double kWiden = 1. + 0x1p-40, kShrink = 1. - 0x1p-40;
 
 struct WallStats {
     long long n_wall = 0, n_tiles = 0, visits = 0, waves = 0;
@@ -75,30 +73,6 @@ __global__ __launch_bounds__(kBlock) void wall_place_k(MeshDev M, const int32_t 
     }
 }
 
-// tile t = the entries [t kWallTile, min((t + 1) kWallTile, W)): centre = the middle of the centroids' bounding box, radius = the largest
-// computed centre-to-centroid distance times kWiden (each distance is within 2^-51 relative of the true one: never too small)
-__global__ __launch_bounds__(kBlock) void wall_tiles_k(const double *__restrict__ tab, int64_t W, int64_t n_tiles, double *__restrict__ tiles) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_tiles) return;
-    const int64_t j0 = t * kWallTile, j1 = j0 + kWallTile < W ? j0 + kWallTile : W;
-    double lo[3], hi[3];
-    for (int q = 0; q < 3; ++q) lo[q] = hi[q] = tab[q * W + j0];
-    for (int64_t j = j0 + 1; j < j1; ++j)
-        for (int q = 0; q < 3; ++q) {
-            const double v = tab[q * W + j];
-            lo[q] = fmin(lo[q], v); hi[q] = fmax(hi[q], v);
-        }
-    double c[3];
-    for (int q = 0; q < 3; ++q) c[q] = lo[q] + (hi[q] - lo[q]) * 0.5;
-    double r = 0.;
-    for (int64_t j = j0; j < j1; ++j) {
-        const double dx = tab[j] - c[0], dy = tab[W + j] - c[1], dz = tab[2 * W + j] - c[2];
-        r = fmax(r, sqrt((dx * dx + dy * dy) + dz * dz));
-    }
-    tiles[t] = c[0]; tiles[n_tiles + t] = c[1]; tiles[2 * n_tiles + t] = c[2];
-    tiles[3 * n_tiles + t] = r * kWiden;
-}
-
 // ------------------------------------------------------------------ the search
 struct WallBest {
     double s, d;  // the smallest s so far and the smallest d_f among the faces that reach it
@@ -128,11 +102,7 @@ __device__ __forceinline__ void wall_tile(const double *__restrict__ tab, int64_
 // Lane i of a wave owns cell 64 wave + i; the idle lanes of the last wave repeat the last owned cell and write nothing, so that every
 // vote of the wave is a vote of cells.  Any order of the walk gives the same bits (a minimum with a tie rule), so the culled search may
 // start where it likes and leave out what cannot matter.
-// The skip of tile t with centre c, radius R for a lane at x with best value b: every entry of the tile lies within R of c, so its s is
-// at least (|x - c| - R)^2; the tile cannot improve or tie when |x - c| > sqrt(b) + R, tested as q kShrink > (sb + R)^2 with
-// q = |x - c|^2 as computed, sb = sqrt(b) kWiden and R widened by wall_tiles_k.  Roundings: q, the computed s of an entry and the
-// square are each within 2^-50 relative; the three factors of 2^-40 dominate them, so a skipped tile holds no entry with computed
-// s <= b.  A NaN anywhere makes the comparison false: the tile is entered.
+// The skip of a tile is sphere_skip (sphere_cull.hpp, with its reasoning): a skipped tile holds no entry with computed s <= b.
 template <bool kCull>
 __global__ __launch_bounds__(kBlock) void wall_search_k(MeshDev M, const double *__restrict__ tab, int64_t W, const double *__restrict__ tiles,
                                                         int64_t n_tiles, double *__restrict__ d, unsigned long long *__restrict__ visits) {
@@ -159,16 +129,13 @@ __global__ __launch_bounds__(kBlock) void wall_search_k(MeshDev M, const double 
         const int64_t seed = __builtin_amdgcn_readfirstlane(near);
         wall_tile(tab, W, seed, x, y, z, b);
         entered = 1;
-        double sb = sqrt(b.s) * kWiden;
+        double sb = sphere_reach(b.s);
         for (int64_t t = 0; t < n_tiles; ++t) {
             if (t == seed) continue;
-            const double dx = x - tx[t], dy = y - ty[t], dz = z - tz[t];
-            const double q = (dx * dx + dy * dy) + dz * dz;
-            const double reach = sb + tr[t];
-            const bool skip = q * kShrink > reach * reach;
+            const bool skip = sphere_skip(sphere_q(x, y, z, tx[t], ty[t], tz[t]), sb, tr[t]);
             if (!__any(!skip)) continue;
             wall_tile(tab, W, t, x, y, z, b);
-            sb = sqrt(b.s) * kWiden;
+            sb = sphere_reach(b.s);
             ++entered;
         }
     }
@@ -245,8 +212,8 @@ int build_table(OrcMesh &m, const std::vector<int32_t> &mask, WallDistance &X) {
     }
     if (gather && W > 0) ORC_TRY(comm_allreduce_sum(X.table.p, (int)(6 * W)));
     if (X.n_tiles > 0) {
-        hipLaunchKernelGGL(wall_tiles_k, dim3((unsigned)((X.n_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx().stream, X.table.p, W, X.n_tiles,
-                           X.tiles.p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(sphere_tiles_k<kWallTile>), dim3((unsigned)((X.n_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx().stream,
+                           X.table.p, X.table.p + W, X.table.p + 2 * W, W, X.n_tiles, X.tiles.p);
         ORC_HIP(hipGetLastError());
     }
     ORC_HIP(hipStreamSynchronize(ctx().stream));  // d_mask, cnt and off are freed on return

@@ -172,6 +172,55 @@ def wall_search_stats(reset=False):
     return dict(zip(("wall_faces", "tile", "tiles", "tile_visits", "waves"), (int(x) for x in out)))
 
 
+def probe_search_stats(reset=False):
+    """orc_debug_probe_search -> dict(tile, tiles, tile_visits, waves, slabs, walk_moves): the cell tiles and slabs of the last point
+    search, and the tile visits, waves and walk moves of all searches since the last reset"""
+    out = (C.c_longlong * 6)()
+    check(lib().orc_debug_probe_search(out, C.c_int(1 if reset else 0)))
+    return dict(zip(("tile", "tiles", "tile_visits", "waves", "slabs", "walk_moves"), (int(x) for x in out)))
+
+
+class Probes:
+    """Points located in the cells of a mesh (OrcProbes*), kept on the device: what Solver.sample and the probe history read.
+    cell (ORC order, as Solver.get_fields()), status (settings.ProbeStatus), steps (moves of the walk), zone (of the boundary face an
+    OUTSIDE point left through, else -1), excess (the largest g of the final cell: <= 0 exactly when inside)."""
+
+    def __init__(self, mesh, points, cull=None, slabs=0):
+        self.mesh = mesh  # keeps the mesh alive: a probe set goes before its mesh
+        self.points = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+        n = len(self.points)
+        st = C.c_int(0)
+        if cull is None and not slabs:
+            ptr = lib().orc_probes_create(mesh.ptr, C.c_int64(n), self.points.ctypes.data_as(_F64), C.byref(st))
+        else:
+            ptr = lib().orc_debug_probes_locate(mesh.ptr, C.c_int64(n), self.points.ctypes.data_as(_F64), C.c_int(0 if cull is False else 1),
+                                                C.c_int(int(slabs)), C.byref(st))
+        check(st.value)
+        self.ptr = C.c_void_p(ptr)
+        self.cell, self.status = np.zeros(n, np.int64), np.zeros(n, np.int32)
+        self.steps, self.zone, self.excess = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n)
+        check(lib().orc_probes_get(self.ptr, self.cell.ctypes.data_as(_I64), self.status.ctypes.data_as(_I32), self.steps.ctypes.data_as(_I32),
+                                   self.zone.ctypes.data_as(_I32), self.excess.ctypes.data_as(_F64)))
+
+    def __del__(self):
+        if getattr(self, "ptr", None):
+            lib().orc_probes_destroy(self.ptr)
+            self.ptr = None
+
+    def __len__(self):
+        return int(lib().orc_probes_count(self.ptr))
+
+    @property
+    def inside(self):
+        return self.status == 0
+
+    def bench_locate(self, cull=True, reps=5):
+        """orc_bench_probe_locate: HIP-event (ms per search and fold, ms per walk) of these points on scratch buffers"""
+        ms = np.zeros(2)
+        check(lib().orc_bench_probe_locate(self.mesh.ptr, self.ptr, C.c_int(1 if cull else 0), C.c_int(reps), ms.ctypes.data_as(_F64)))
+        return float(ms[0]), float(ms[1])
+
+
 class Mesh:
     """Device-resident mesh (OrcMesh*)."""
 
@@ -259,6 +308,15 @@ class Mesh:
         ms = C.c_double(0.0)
         check(lib().orc_bench_wall_distance(self.ptr, C.c_int(1 if cull else 0), C.c_int(reps), C.byref(ms)))
         return ms.value
+
+    def locate(self, points, cull=None, slabs=0):
+        """orc_probes_create: the points [n, 3] located in the cells of this mesh, all at once on the device -> Probes.  cull=False
+        (every cell for every point) and slabs (a forced number of cell slabs) go through orc_debug_probes_locate: same result."""
+        return Probes(self, points, cull, slabs)
+
+    def probe_search_stats(self, reset=False):
+        """the counters of the point search (module function probe_search_stats)"""
+        return probe_search_stats(reset)
 
     def matrix_pattern(self):
         rp = np.empty(self.n_cells + 1, np.int64)

@@ -201,3 +201,19 @@ class TimeStatistics(C.Structure):
             s.groups = int(groups)
         s.start_step, s.interval = int(start_step), int(interval)
         return s
+
+
+class ProbeStatus:  # include/orc_types.h OrcProbeStatus
+    INSIDE, OUTSIDE, WALK_LIMIT = 0, 1, 2
+
+
+class ProbeField:  # include/orc_types.h OrcProbeField (bit = 1 << value)
+    U, V, W, P, PHI, MU = 0, 1, 2, 3, 4, 5
+    N = 6
+
+
+class ProbeInterpolation:  # include/orc_types.h OrcProbeInterpolation
+    CELL, LINEAR = 0, 1
+
+
+PROBE_WALK_LIMIT = 64  # include/orc_types.h ORC_PROBE_WALK_LIMIT: moves of a walk

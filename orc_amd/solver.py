@@ -263,6 +263,21 @@ STAT_BOUNDARY_NAMES = BOUNDARY_NAMES[:5]  # the boundary maps whose running mean
 _STAT_MEAN, _STAT_STRESS, _STAT_SCALAR = STATISTIC_NAMES[:4], STATISTIC_NAMES[4:11], STATISTIC_NAMES[12:]
 
 
+# orc_types.h OrcProbeField, by value: what Solver.sample and the probe history read at a point
+PROBE_NAMES = ("u", "v", "w", "p", "phi", "mu")
+
+
+def _interpolation(x):
+    """'cell' / 'linear' or a settings.ProbeInterpolation value -> the value"""
+    return {"cell": 0, "linear": 1}[x.lower()] if isinstance(x, str) else int(x)
+
+
+def _probe_rows(out, mask, names):
+    order = [i for i in range(len(PROBE_NAMES)) if mask >> i & 1]
+    rows = {PROBE_NAMES[f]: out[q] for q, f in enumerate(order)}
+    return {name: rows[name] for name in names}
+
+
 class Solver:
     """Device-resident state of one solve_steady call (OrcSolver*): what bench.py drives."""
 
@@ -625,6 +640,71 @@ class Solver:
         ms = np.zeros(2)
         check(lib().orc_bench_time_statistics(self.ptr, C.c_int(reps), _p(ms)))
         return float(ms[0]), float(ms[1])
+
+    # ---------------------------------------------------------------- point probes (orc_solver_sample_probes, orc_solver_set_probe_history)
+    def sample(self, probes, fields=("u", "v", "w", "p"), interpolation="linear", raise_on_error=True):
+        """orc_solver_sample_probes: {name: ndarray[len(probes)]} of the fields (PROBE_NAMES or a bit mask) at the points of a
+        Mesh.locate() result; interpolation 'cell' or 'linear' (or a settings.ProbeInterpolation value).  Points outside the mesh are
+        sampled at their final cell: probes.status tells.  Reads only.  (raise_on_error=False: (status, dict))"""
+        mask, names = _mask_of(fields, PROBE_NAMES)
+        n = len(probes)
+        out = np.zeros((max(bin(mask).count("1"), 1), n))
+        st = lib().orc_solver_sample_probes(self.ptr, probes.ptr if probes is not None else None, C.c_uint32(mask & 0xFFFFFFFF),
+                                            C.c_int32(_interpolation(interpolation)), _p(out))
+        res = _probe_rows(out, mask, names) if st == 0 else {}
+        if raise_on_error:
+            check(st)
+            return res
+        return st, res
+
+    def sample_line(self, a, b, n, **kw):
+        """n points from a to b (both included), located and sampled -> (points [n, 3], Probes, {name: ndarray[n]}); kw as sample()"""
+        a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        t = np.linspace(0.0, 1.0, n)[:, None] if n > 1 else np.zeros((1, 1))
+        points = a[None, :] + t * (b - a)[None, :]
+        probes = self.mesh.locate(points)
+        return points, probes, self.sample(probes, **kw)
+
+    def set_probe_history(self, probes=None, fields=("u", "v", "w", "p"), interpolation="linear", interval=1, raise_on_error=True):
+        """orc_solver_set_probe_history: from now on advance() appends one record of the fields at the probes after every `interval`-th
+        step (steps counted from 1 since enabling); probes=None turns the history off and drops it.  Reads only: fields and reports
+        keep their bits, and a step gains no synchronisation."""
+        if probes is None:
+            st = lib().orc_solver_set_probe_history(self.ptr, None, C.c_uint32(0), C.c_int32(0), C.c_uint64(1))
+            mask, names = 0, []
+        else:
+            mask, names = _mask_of(fields, PROBE_NAMES)
+            st = lib().orc_solver_set_probe_history(self.ptr, probes.ptr, C.c_uint32(mask & 0xFFFFFFFF), C.c_int32(_interpolation(interpolation)),
+                                                    C.c_uint64(interval))
+        if st == 0:
+            self._probe_history = (probes, mask, names)  # keeps the probe set alive while the history reads it
+        if raise_on_error:
+            check(st)
+        return st
+
+    def record_probes(self, tag=0.0, raise_on_error=True):
+        """orc_solver_record_probes: one record of the current state with `tag` in the time slot (steady runs)"""
+        st = lib().orc_solver_record_probes(self.ptr, C.c_double(tag))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def probe_history_count(self):
+        """records kept (-1 while the history is off)"""
+        return int(lib().orc_solver_probe_history_count(self.ptr))
+
+    def probe_history(self, first=0, count=None):
+        """the records [first, first + count) -> (times [k], {name: ndarray (k, n_points)}) (count=None: all from first)"""
+        probes, mask, names = getattr(self, "_probe_history", None) or (None, 0, [])
+        have = self.probe_history_count()
+        if count is None:
+            count = max(have - first, 0)
+        k, n = max(bin(mask).count("1"), 1), len(probes) if probes is not None else 0
+        times, out = np.zeros(count), np.zeros((count, k, max(n, 1)))
+        check(lib().orc_solver_probe_history(self.ptr, C.c_uint64(first), C.c_uint64(count), _p(times), _p(out)))
+        order = [i for i in range(len(PROBE_NAMES)) if mask >> i & 1]
+        rows = {PROBE_NAMES[f]: np.ascontiguousarray(out[:, q, :n]) for q, f in enumerate(order)}
+        return times, {name: rows[name] for name in names}
 
     def surface_report(self, origin=None, raise_on_error=True):
         """orc_solver_surface_report: per-zone force, moment, mass and momentum flow, area and mean pressure of the current
