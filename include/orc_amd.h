@@ -656,6 +656,50 @@ OrcProbes *orc_debug_probes_locate(OrcMesh *m, int64_t n_points, const double *x
 int orc_debug_probe_search(long long out[6], int reset);
 int orc_bench_probe_locate(OrcMesh *m, const OrcProbes *p, int cull, int reps, double avg_ms[2]);
 
+/* ---------- tracer particles (new-build extension, orc_types.h OrcTracerStatus / OrcTracerSettings) ----------
+ * A tracer set is a list of massless particles in the cells of one mesh, kept on the device: per particle the position, the cell, the
+ * OrcTracerStatus, the zone it left through (-1 otherwise), the age (the signed sum of the accepted h) and the accepted substeps.  A
+ * solver of the same mesh moves the set through its current u, v, w (orc_types.h, DESIGN.md §3 "Tracer particles": the substep and its
+ * operator order).  Opt-in and read-only towards mesh and solver: a solver that calls no tracer entry launches what it launched before.
+ *  - orc_tracers_create: the seeds xyz (point-major) located exactly as orc_probes_create locates points; INSIDE seeds start ACTIVE,
+ *    OUTSIDE seeds LEFT with the walk's zone, WALK_LIMIT seeds WALK_LIMIT, and the latter two never move.  NULL + *status on failure.  A
+ *    partitioned mesh is refused.  Destroy a set before its mesh, and after any solver that tracks it.
+ *  - orc_tracers_get: each output [n] (xyz [3 n] point-major, cell in ORC order) or NULL.
+ *  - orc_solver_advect_tracers: up to n_substeps substeps of every particle in the solver's current velocity.  record_stride > 0 (which
+ *    n_substeps must be a multiple of, K = n_substeps / record_stride) also returns the path: record k of path[K + 1][3][n] holds the
+ *    positions after k record_stride substeps of this call, record 0 those at entry, a stopped particle repeating its last position;
+ *    path_len[i] = min(K + 1, 1 + ceil(a_i / record_stride)) with a_i the substeps particle i accepted in this call (may be NULL).  One
+ *    launch per record, no synchronisation between them.  With LINEAR a zone type the assembly refuses returns ORC_ERR_UNSUPPORTED_BC
+ *    and a singular least-squares system ORC_ERR_SINGULAR_MATRIX, as orc_solver_sample_probes; the set is then as it was before the call.
+ *  - orc_solver_sample_tracers: orc_solver_sample_probes at the particles' present positions and cells.
+ *  - orc_solver_set_tracer_tracking: t == NULL turns it off; otherwise from now on every step of orc_solver_advance moves the set by
+ *    substeps_per_step substeps of h = dt / substeps_per_step in the velocity of the new time level (first order in time),
+ *    after the probe history and without a synchronisation.  Needs orc_solver_set_transient, step_mode TIME and direction +1; `step` is
+ *    ignored.  A gradient failure of a step is returned by the next step or the next call of this entry.  orc_solver_snapshot /
+ *    orc_solver_restore leave the set alone.
+ *  - orc_write_vtu_lines: host only; one VTK_POLY_LINE cell per line (VTK_VERTEX for a line of one point) over points
+ *    [line_ptr[i], line_ptr[i + 1]) with point data arrays (component-major per array), in the conventions of orc_write_vtu_faces.
+ *  - orc_bench_tracers: HIP-event average ms over `reps` of one launch of n_substeps substeps from the set's state into scratch buffers.
+ * Every compute entry looks for a device first (ORC_ERR_NO_DEVICE without one).  Refused with ORC_ERR_BAD_ARGUMENT, solver, mesh and set
+ * unchanged: null arguments; n < 1; a coordinate that is not finite; a partitioned mesh; a set of another mesh; an unknown scheme,
+ * interpolation, step mode or direction; a step that is not positive and finite (except under tracking); a min_speed that is not >= 0;
+ * record_stride > 0 with n_substeps not a multiple of it or with a null path; tracking without the transient arm, with LENGTH, with
+ * direction -1 or with substeps_per_step = 0.  LINEAR with an unsupported gradient scheme: ORC_ERR_UNSUPPORTED_SCHEME. */
+typedef struct OrcTracers OrcTracers;
+void orc_tracer_settings_default(OrcTracerSettings *c); /* RK2, LINEAR, LENGTH, +1, step 0 (must be set), min_speed 0 */
+OrcTracers *orc_tracers_create(OrcMesh *m, int64_t n, const double *xyz /*[3 * n] point-major*/, int *status);
+void orc_tracers_destroy(OrcTracers *t);
+int64_t orc_tracers_count(const OrcTracers *t);
+int orc_tracers_get(const OrcTracers *t, double *xyz, int64_t *cell, int32_t *status, int32_t *zone, double *age, int64_t *steps);
+int orc_solver_advect_tracers(OrcSolver *s, OrcTracers *t, const OrcTracerSettings *c, uint64_t n_substeps, uint64_t record_stride /*0 = no path*/,
+                              double *path /*[K + 1][3][n]*/, int32_t *path_len /*[n]*/);
+int orc_solver_sample_tracers(OrcSolver *s, const OrcTracers *t, uint32_t field_mask, int32_t interpolation,
+                              double *out /*[popcount(field_mask) * n]*/);
+int orc_solver_set_tracer_tracking(OrcSolver *s, OrcTracers *t /*NULL = off*/, const OrcTracerSettings *c, uint32_t substeps_per_step);
+int orc_write_vtu_lines(const char *path, int64_t n_lines, const int64_t *line_ptr /*[n_lines + 1]*/, const double *points /*[3 * line_ptr[n_lines]]*/,
+                        int32_t n_arrays, const char *const *names, const int32_t *components, const double *const *data /*per point*/, int32_t encoding);
+int orc_bench_tracers(OrcSolver *s, const OrcTracers *t, const OrcTracerSettings *c, uint64_t n_substeps, int reps, double *avg_ms);
+
 /* ---------- measurement hooks (bench.py): HIP-event timed launches of single kernels ---------- */
 /* y = A x with the momentum matrix a_u of the solver, `reps` launches; returns average ms per launch */
 int orc_bench_spmv(OrcSolver *s, int reps, double *avg_ms, double *checksum);

@@ -367,6 +367,29 @@ enum OrcProbeInterpolation {
                             gradient_reconstruction (a row of orc_calculate_gradients, bit for bit), r = x - x_P; PHI and MU: the cell's */
 };
 
+/* Tracer particles (new-build extension; orc_amd.h: orc_tracers_create, orc_solver_advect_tracers): massless particles moved through
+ * the cells in the solver's velocity.  A substep of an ACTIVE particle at (x, P): U1 = velocity(x, P); h = direction step (TIME) or
+ * (direction step) / |U1| (LENGTH; STAGNANT unless |U1| > min_speed); EULER xn = x + h U1, RK2 xm = x + (0.5 h) U1, U2 at xm in the
+ * cell the probes' walk reaches from P, xn = x + h U2; the walk from there to xn accepts the substep (INSIDE) or stops the particle at
+ * its last accepted position (LEFT through a boundary face's zone, or WALK_LIMIT).  DESIGN.md §3 "Tracer particles" fixes the operator
+ * order. */
+enum OrcTracerStatus {
+    ORC_TRACER_ACTIVE = 0,     /* moves */
+    ORC_TRACER_LEFT = 1,       /* a stage walk ended at a boundary face: zone tells which; position and cell are the last accepted ones */
+    ORC_TRACER_WALK_LIMIT = 2, /* a stage walk made ORC_PROBE_WALK_LIMIT moves without finding the cell */
+    ORC_TRACER_STAGNANT = 3    /* LENGTH mode: the speed at the particle is not above min_speed (or is NaN) */
+};
+enum OrcTracerScheme { ORC_TRACER_EULER = 0, ORC_TRACER_RK2 = 1 /* midpoint */ };
+enum OrcTracerStepMode { ORC_TRACER_STEP_TIME = 0 /* h = direction step */, ORC_TRACER_STEP_LENGTH = 1 /* |xn - x| about step */ };
+typedef struct OrcTracerSettings {
+    int32_t scheme;        /* OrcTracerScheme */
+    int32_t interpolation; /* OrcProbeInterpolation */
+    int32_t step_mode;     /* OrcTracerStepMode */
+    int32_t direction;     /* +1 with the flow, -1 against it */
+    double step;           /* > 0: a time (TIME) or a length (LENGTH) */
+    double min_speed;      /* >= 0, LENGTH only */
+} OrcTracerSettings;       /* 32 bytes */
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,29 @@ def lib():
             L.orc_debug_probe_search.restype = C.c_int
             L.orc_bench_probe_locate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _f64]
             L.orc_bench_probe_locate.restype = C.c_int
+        # tracer particles (orc_amd.h "tracer particles"): full signatures
+        if hasattr(L, "orc_tracers_create"):
+            _f64, _i64, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+            L.orc_tracer_settings_default.argtypes = [C.c_void_p]
+            L.orc_tracer_settings_default.restype = None
+            L.orc_tracers_create.argtypes = [C.c_void_p, C.c_int64, _f64, C.POINTER(C.c_int)]
+            L.orc_tracers_create.restype = C.c_void_p
+            L.orc_tracers_destroy.argtypes = [C.c_void_p]
+            L.orc_tracers_destroy.restype = None
+            L.orc_tracers_count.argtypes = [C.c_void_p]
+            L.orc_tracers_count.restype = C.c_int64
+            L.orc_tracers_get.argtypes = [C.c_void_p, _f64, _i64, _i32, _i32, _f64, _i64]
+            L.orc_tracers_get.restype = C.c_int
+            L.orc_solver_advect_tracers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, _f64, _i32]
+            L.orc_solver_advect_tracers.restype = C.c_int
+            L.orc_solver_sample_tracers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, _f64]
+            L.orc_solver_sample_tracers.restype = C.c_int
+            L.orc_solver_set_tracer_tracking.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            L.orc_solver_set_tracer_tracking.restype = C.c_int
+            L.orc_write_vtu_lines.argtypes = [C.c_char_p, C.c_int64, _i64, _f64, C.c_int32, C.POINTER(C.c_char_p), _i32, C.POINTER(_f64), C.c_int32]
+            L.orc_write_vtu_lines.restype = C.c_int
+            L.orc_bench_tracers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, _f64]
+            L.orc_bench_tracers.restype = C.c_int
         # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
         if hasattr(L, "orc_debug_amg_setup_stats"):
             L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]

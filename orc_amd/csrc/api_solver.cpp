@@ -524,6 +524,7 @@ int advance_one(SolverState &st, double *row /*10*/) {
     ORC_TRY(scalar_step_dev(st));  // scalar arm on: its levels shift and it is solved once on this step's flow
     ORC_TRY(stats_step_dev(st));   // statistics arm on: the step is counted and, when due, sampled with weight dt
     ORC_TRY(probes_step_dev(st));  // probe history on: the step is counted and, when due, recorded at the time reached
+    ORC_TRY(tracers_step_dev(st)); // tracer tracking on: the set moves through the velocity just reached
     if (row) {
         std::copy(rep, rep + 8, row);
         row[8] = (double)used;

@@ -293,6 +293,31 @@ struct SolverState {
             times.clear(); values.clear();
         }
     } ph;
+    // Tracer tracking (orc_solver_set_tracer_tracking, tracers.hip): off unless enabled.  Every step of orc_solver_advance moves the set
+    // by `substeps` substeps of h in the new velocity; the kernel's status word is copied to the pinned `raw` behind it and looked at
+    // by the next step.  Reads the fields, never writes them; snapshot / restore leave the set alone.
+    struct TracerTracking {
+        bool on = false;
+        OrcTracers *set = nullptr;
+        OrcTracerSettings c{};
+        uint32_t substeps = 0;
+        double h = 0.;                    // dt / substeps, computed once on the host
+        DevBuf<int> status;
+        int *raw = nullptr;               // pinned
+        hipEvent_t copied = nullptr;
+        bool pending = false;
+        TracerTracking() = default;
+        TracerTracking(const TracerTracking &) = delete;
+        TracerTracking &operator=(const TracerTracking &) = delete;
+        ~TracerTracking() { clear(); }
+        void clear() {
+            if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
+            if (raw) (void)hipHostFree(raw);
+            copied = nullptr; raw = nullptr;
+            status.release();
+            on = false; pending = false; set = nullptr; substeps = 0; h = 0.;
+        }
+    } tt;
 };
 
 int mesh_upload(OrcMesh &m, int64_t n_own, int64_t n_cells, int64_t n_faces, int32_t n_zones, const int64_t *face_c0, const int64_t *face_c1,
@@ -392,6 +417,9 @@ int stats_step_dev(SolverState &s);
 // probe history (probes.hip): what orc_solver_advance runs after stats_step_dev — counts the step and, when the history is on and the
 // step is due, samples one record on the device and starts its copy to the host; asynchronous on ctx().stream, nothing while it is off
 int probes_step_dev(SolverState &s);
+// tracer tracking (tracers.hip): what orc_solver_advance runs after probes_step_dev — while tracking is on, one launch that moves the
+// set through the step's velocity; asynchronous on ctx().stream, nothing while it is off
+int tracers_step_dev(SolverState &s);
 
 }  // namespace orc
 

@@ -26,17 +26,9 @@
 
 #include "assembly.hpp"
 #include "gradient_cell.hpp"
+#include "point_walk.hpp"
+#include "probes.hpp"
 #include "sphere_cull.hpp"
-
-// The located points of one mesh, on the device in the search's (Morton) order: position k holds the caller's point order[k].
-struct OrcProbes {
-    OrcMesh *mesh = nullptr;
-    int64_t n = 0;
-    std::vector<int64_t> order;
-    orc::DevBuf<double> x, y, z;                    // [n]
-    orc::DevBuf<int32_t> cell, status, steps, zone;  // [n]: the final cell (internal numbering), OrcProbeStatus, moves, zone or -1
-    orc::DevBuf<double> excess, off;                // [n] the last largest g; [3][n] x - x_cell
-};
 
 namespace orc {
 
@@ -182,33 +174,17 @@ struct WalkArgs {
     unsigned long long *moves;
 };
 
-// One lane per point.  Every cell the walk reaches is c0 or c1 >= 0 of a face of an owned cell of an unpartitioned mesh: below n_cells.
+// One lane per point: the walk of point_walk.hpp from the search's start cell.
 __global__ __launch_bounds__(kBlock) void probe_walk_k(MeshDev M, WalkArgs A) {
     int total = 0;
     GRID_STRIDE(i, A.n_pts) {
         const double x = A.x[i], y = A.y[i], z = A.z[i];
-        int P = A.start[i], moves = 0, st = ORC_PROBE_STATUS_INSIDE, zn = -1;
-        double gbest;
-        for (;;) {
-            int fbest = -1;
-            gbest = -INFINITY;
-            for (int q = M.cfp[P]; q < M.cfp[P + 1]; ++q) {
-                const int f = M.cf[q];
-                const double rx = x - M.fcx[f], ry = y - M.fcy[f], rz = z - M.fcz[f];
-                double g = (rx * M.nx[f] + ry * M.ny[f]) + rz * M.nz[f];
-                if (M.c0[f] != P) g = -g;
-                if (fbest < 0 || g > gbest) { gbest = g; fbest = f; }
-            }
-            if (fbest < 0 || gbest <= 0.) { st = ORC_PROBE_STATUS_INSIDE; break; }
-            if (M.c1[fbest] < 0) { st = ORC_PROBE_STATUS_OUTSIDE; zn = M.fzone[fbest]; break; }
-            if (moves == ORC_PROBE_WALK_LIMIT) { st = ORC_PROBE_STATUS_WALK_LIMIT; break; }
-            P = M.c0[fbest] == P ? M.c1[fbest] : M.c0[fbest];
-            ++moves;
-        }
-        A.cell[i] = P; A.status[i] = st; A.steps[i] = moves; A.zone[i] = zn;
-        A.excess[i] = gbest;
+        int P = A.start[i];
+        const WalkEnd e = point_walk(M, x, y, z, P);
+        A.cell[i] = P; A.status[i] = e.status; A.steps[i] = e.moves; A.zone[i] = e.zone;
+        A.excess[i] = e.g;
         A.off[i] = x - M.ccx[P]; A.off[A.n_pts + i] = y - M.ccy[P]; A.off[2 * A.n_pts + i] = z - M.ccz[P];
-        total += moves;
+        total += e.moves;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) total += __shfl_down(total, o, 64);
@@ -431,9 +407,14 @@ void unsort(const std::vector<int64_t> &order, const T *src, U *dst) {
 }
 
 // ------------------------------------------------------------------ sampling
+int validate_fields(const SolverState &s, uint32_t mask, int32_t interpolation);
 int validate_sample(const SolverState &s, const OrcProbes *p, uint32_t mask, int32_t interpolation) {
     if (!p) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: null probe set");
     if (p->mesh != s.mesh) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: the probe set was located in another mesh");
+    return validate_fields(s, mask, interpolation);
+}
+
+int validate_fields(const SolverState &s, uint32_t mask, int32_t interpolation) {
     if (mask == 0 || (mask & ~kAllFields)) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: mask 0x%x selects nothing or an unknown field", mask);
     if ((mask & (1u << ORC_PROBE_PHI)) && !s.sc.on) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: PHI needs the scalar arm (orc_solver_set_scalar)");
     if (interpolation != ORC_PROBE_CELL && interpolation != ORC_PROBE_LINEAR) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: unknown interpolation %d", interpolation);
@@ -443,14 +424,16 @@ int validate_sample(const SolverState &s, const OrcProbes *p, uint32_t mask, int
     return ORC_OK;
 }
 
-// the fields of `mask` at the points of p into out_dev [popcount][n] (the set's device order), asynchronous on ctx().stream
-int launch_sample(const SolverState &s, const OrcProbes &p, uint32_t mask, int32_t interpolation, double *out_dev, int *status_dev) {
+// the fields of `mask` at n points given by cell and offset [3][n] into out_dev [popcount][n] (the set's device order), asynchronous on
+// ctx().stream
+int launch_sample(const SolverState &s, const int32_t *cell, const double *off, int64_t n, uint32_t mask, int32_t interpolation, double *out_dev,
+                  int *status_dev) {
     SampleArgs A{s.u.p, s.v.p, s.w.p, s.p.p, (mask & (1u << ORC_PROBE_PHI)) ? s.sc.phi.p : nullptr, s.cell_viscosity(), s.mu,
-                 p.cell.p, p.off.p, p.n, out_dev, mask, interpolation == ORC_PROBE_LINEAR ? 1 : 0, s.settings.q1_compat};
+                 cell, off, n, out_dev, mask, interpolation == ORC_PROBE_LINEAR ? 1 : 0, s.settings.q1_compat};
     if (s.settings.gradient_reconstruction == ORC_GRAD_LEAST_SQUARES)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(probe_sample_k<true>), dim3(grid_for(p.n)), dim3(kBlock), 0, ctx().stream, s.mesh->dev(), A, status_dev);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(probe_sample_k<true>), dim3(grid_for(n)), dim3(kBlock), 0, ctx().stream, s.mesh->dev(), A, status_dev);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(probe_sample_k<false>), dim3(grid_for(p.n)), dim3(kBlock), 0, ctx().stream, s.mesh->dev(), A, status_dev);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(probe_sample_k<false>), dim3(grid_for(n)), dim3(kBlock), 0, ctx().stream, s.mesh->dev(), A, status_dev);
     ORC_HIP(hipGetLastError());
     return ORC_OK;
 }
@@ -487,7 +470,7 @@ int history_flush(SolverState &s) {
 int history_enqueue(SolverState &s, double time) {
     SolverState::ProbeHistory &H = s.ph;
     const size_t len = (size_t)H.n_fields * (size_t)H.probes->n;
-    ORC_TRY(launch_sample(s, *H.probes, H.mask, H.interpolation, H.rec.p, H.status.p));
+    ORC_TRY(launch_sample(s, H.probes->cell.p, H.probes->off.p, H.probes->n, H.mask, H.interpolation, H.rec.p, H.status.p));
     ORC_HIP(hipMemcpyAsync(H.raw, H.rec.p, len * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
     ORC_HIP(hipMemcpyAsync(H.raw + len, H.status.p, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
     ORC_HIP(hipEventRecord(H.copied, ctx().stream));
@@ -497,6 +480,14 @@ int history_enqueue(SolverState &s, double time) {
 }
 
 }  // namespace
+
+OrcProbes *probes_locate(OrcMesh *m, int64_t n, const double *xyz, int *status) { return locate(m, n, xyz, true, 0, status); }
+int probes_launch_sample(const SolverState &s, const int32_t *cell, const double *off, int64_t n, uint32_t mask, int32_t interpolation,
+                         double *out_dev, int *status_dev) {
+    return launch_sample(s, cell, off, n, mask, interpolation, out_dev, status_dev);
+}
+int probes_validate_fields(const SolverState &s, uint32_t mask, int32_t interpolation) { return validate_fields(s, mask, interpolation); }
+int probes_sample_status(int h) { return sample_status(h); }
 
 int probes_step_dev(SolverState &s) {
     SolverState::ProbeHistory &H = s.ph;
@@ -563,7 +554,7 @@ int orc_solver_sample_probes(OrcSolver *s, const OrcProbes *p, uint32_t field_ma
     ORC_TRY(dev.alloc((size_t)k * n));
     ORC_TRY(status.alloc(1));
     ORC_TRY(status.zero());
-    ORC_TRY(launch_sample(st, *p, field_mask, interpolation, dev.p, status.p));
+    ORC_TRY(launch_sample(st, p->cell.p, p->off.p, p->n, field_mask, interpolation, dev.p, status.p));
     std::vector<double> h((size_t)k * n);
     ORC_TRY(dev.download(h.data(), h.size()));
     int hs = 0;
@@ -591,7 +582,7 @@ int orc_solver_set_probe_history(OrcSolver *s, const OrcProbes *p, uint32_t fiel
     ORC_TRY(rec.alloc(len));
     ORC_TRY(status.alloc(1));
     ORC_TRY(status.zero());
-    ORC_TRY(launch_sample(st, *p, field_mask, interpolation, rec.p, status.p));
+    ORC_TRY(launch_sample(st, p->cell.p, p->off.p, p->n, field_mask, interpolation, rec.p, status.p));
     int hs = 0;
     ORC_TRY(status.download(&hs, 1));
     ORC_TRY(sample_status(hs));

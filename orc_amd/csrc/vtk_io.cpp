@@ -17,7 +17,7 @@ namespace {
 
 using orc::set_error;
 
-constexpr uint8_t kVtkPolygon = 7, kVtkTetra = 10, kVtkHexahedron = 12, kVtkPolyhedron = 42;
+constexpr uint8_t kVtkVertex = 1, kVtkPolyLine = 4, kVtkPolygon = 7, kVtkTetra = 10, kVtkHexahedron = 12, kVtkPolyhedron = 42;
 
 struct P3 {
     double x, y, z;
@@ -154,8 +154,10 @@ struct Writer {
     }
 };
 
-// renumber the used points ascending, then write the file
-int finish(const char *path, int64_t n_points, const double *points, Piece &P, const Arrays &A, int64_t n_items, int32_t encoding) {
+// renumber the used points ascending, then write the file; the arrays are cell data of n_items cells, or (point_data, every point
+// used) point data of n_points points
+int finish(const char *path, int64_t n_points, const double *points, Piece &P, const Arrays &A, int64_t n_items, int32_t encoding,
+           bool point_data = false) {
     std::vector<int64_t> new_id((size_t)n_points, -1);
     for (int64_t v : P.connectivity) new_id[(size_t)v] = 0;
     if (P.any_polyhedron)
@@ -189,7 +191,7 @@ int finish(const char *path, int64_t n_points, const double *points, Piece &P, c
     if (!W.f) return set_error(ORC_ERR_IO, "write_vtu: cannot open '%s' for writing", path);
     FILE *f = W.f;
     fprintf(f, "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"1.0\" byte_order=\"LittleEndian\" header_type=\"UInt64\">\n");
-    fprintf(f, "  <UnstructuredGrid>\n    <Piece NumberOfPoints=\"%lld\" NumberOfCells=\"%lld\">\n", (long long)used, (long long)n_items);
+    fprintf(f, "  <UnstructuredGrid>\n    <Piece NumberOfPoints=\"%lld\" NumberOfCells=\"%lld\">\n", (long long)used, (long long)n_items);  // n_items: still the cells
     fprintf(f, "      <Points>\n");
     W.array("Float64", "Points", 3, xyz, "%.17g");
     fprintf(f, "      </Points>\n      <Cells>\n");
@@ -200,7 +202,8 @@ int finish(const char *path, int64_t n_points, const double *points, Piece &P, c
         W.array("Int64", "faces", 0, P.faces, "%lld");
         W.array("Int64", "faceoffsets", 0, P.faceoffsets, "%lld");
     }
-    fprintf(f, "      </Cells>\n      <CellData>\n");
+    fprintf(f, "      </Cells>\n      <%s>\n", point_data ? "PointData" : "CellData");
+    if (point_data) n_items = used;
     std::vector<double> tuples;
     for (int32_t a = 0; a < A.n; ++a) {  // structure-of-arrays by component -> VTK's tuples
         const int32_t k = A.components[a];
@@ -209,7 +212,7 @@ int finish(const char *path, int64_t n_points, const double *points, Piece &P, c
             for (int64_t c = 0; c < n_items; ++c) tuples[(size_t)c * k + q] = A.data[a][(size_t)q * n_items + c];
         W.array("Float64", A.names[a], k, tuples, "%.17g");
     }
-    fprintf(f, "      </CellData>\n    </Piece>\n  </UnstructuredGrid>\n");
+    fprintf(f, "      </%s>\n    </Piece>\n  </UnstructuredGrid>\n", point_data ? "PointData" : "CellData");
     if (W.raw) {
         fprintf(f, "  <AppendedData encoding=\"raw\">\n_");
         for (const std::vector<char> &blk : W.appended) {
@@ -299,6 +302,25 @@ int orc_write_vtu_faces(const char *path, int64_t n_points, const double *points
         P.types.push_back(kVtkPolygon);
     }
     return finish(path, n_points, points, P, A, n_faces, encoding);
+}
+
+int orc_write_vtu_lines(const char *path, int64_t n_lines, const int64_t *line_ptr, const double *points, int32_t n_arrays, const char *const *names,
+                        const int32_t *components, const double *const *data, int32_t encoding) {
+    if (!path || n_lines < 0 || !line_ptr) return set_error(ORC_ERR_BAD_ARGUMENT, "write_vtu_lines: null or negative argument");
+    Arrays A{n_arrays, names, components, data};
+    ORC_TRY(check_arrays(A, encoding));
+    if (line_ptr[0] != 0) return set_error(ORC_ERR_BAD_ARGUMENT, "write_vtu_lines: line_ptr must start at 0");
+    for (int64_t i = 0; i < n_lines; ++i)
+        if (line_ptr[i + 1] <= line_ptr[i]) return set_error(ORC_ERR_BAD_ARGUMENT, "write_vtu_lines: line %lld has no point (line_ptr must increase)", (long long)i);
+    const int64_t n_points = line_ptr[n_lines];
+    if (n_points > 0 && !points) return set_error(ORC_ERR_BAD_ARGUMENT, "write_vtu_lines: null points");
+    Piece P;
+    for (int64_t i = 0; i < n_lines; ++i) {
+        for (int64_t v = line_ptr[i]; v < line_ptr[i + 1]; ++v) P.connectivity.push_back(v);
+        P.offsets.push_back(line_ptr[i + 1]);
+        P.types.push_back(line_ptr[i + 1] - line_ptr[i] == 1 ? kVtkVertex : kVtkPolyLine);
+    }
+    return finish(path, n_points, points, P, A, n_lines, encoding, true);
 }
 
 }  // extern "C"

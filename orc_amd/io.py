@@ -179,3 +179,14 @@ def write_vtu_boundary(path, mesh_data, boundary_fields, extra_arrays=None, enco
     keep, k, names, comps, data = _vtu_tables(arrays, len(faces))
     check(lib().orc_write_vtu_faces(str(path).encode(), C.c_int64(len(vert)), _p(vert), C.c_int64(len(faces)), _p(faces, _I64), _p(fnp, _I64),
                                     _p(fn, _I64), C.c_int32(k), names, comps, data, C.c_int32(_ENCODINGS[encoding])))
+
+
+def write_vtu_lines(path, lines, point_data=None, encoding="raw"):
+    """orc_write_vtu_lines: `lines`, a list of [m_i, 3] arrays (Solver.streamlines), as VTK_POLY_LINE cells (VTK_VERTEX for a single
+    point) of a VTK XML UnstructuredGrid; point_data {name: ndarray[sum m_i] or [sum m_i, k]} in the order of the concatenated lines."""
+    lines = [np.asarray(a, dtype=np.float64).reshape(-1, 3) for a in lines]
+    ptr = np.concatenate([[0], np.cumsum([len(a) for a in lines])]).astype(np.int64)
+    pts = np.ascontiguousarray(np.concatenate(lines)) if lines else np.zeros((0, 3))
+    keep, k, names, comps, data = _vtu_tables(point_data or {}, int(ptr[-1]))
+    check(lib().orc_write_vtu_lines(str(path).encode(), C.c_int64(len(lines)), _p(ptr, _I64), _p(pts), C.c_int32(k), names, comps, data,
+                                    C.c_int32(_ENCODINGS[encoding])))

@@ -221,6 +221,56 @@ class Probes:
         return float(ms[0]), float(ms[1])
 
 
+class Tracers:
+    """Tracer particles in the cells of a mesh (OrcTracers*), kept on the device: what Solver.advect moves and Solver.sample_tracers
+    reads.  positions [n, 3], cell (ORC order), status (settings.TracerStatus), zone (of the boundary face a LEFT particle went
+    through, else -1), age (the signed sum of the accepted h), steps (accepted substeps): each read from the device when asked for."""
+
+    def __init__(self, mesh, points):
+        self.mesh = mesh  # keeps the mesh alive: a tracer set goes before its mesh
+        self.seeds = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+        st = C.c_int(0)
+        ptr = lib().orc_tracers_create(mesh.ptr, C.c_int64(len(self.seeds)), self.seeds.ctypes.data_as(_F64), C.byref(st))
+        check(st.value)
+        self.ptr = C.c_void_p(ptr)
+
+    def __del__(self):
+        if getattr(self, "ptr", None):
+            lib().orc_tracers_destroy(self.ptr)
+            self.ptr = None
+
+    def __len__(self):
+        return int(lib().orc_tracers_count(self.ptr))
+
+    def get(self):
+        """orc_tracers_get: dict(positions, cell, status, zone, age, steps) in one call"""
+        n = len(self)
+        out = dict(positions=np.zeros((n, 3)), cell=np.zeros(n, np.int64), status=np.zeros(n, np.int32), zone=np.zeros(n, np.int32),
+                   age=np.zeros(n), steps=np.zeros(n, np.int64))
+        check(lib().orc_tracers_get(self.ptr, out["positions"].ctypes.data_as(_F64), out["cell"].ctypes.data_as(_I64),
+                                    out["status"].ctypes.data_as(_I32), out["zone"].ctypes.data_as(_I32), out["age"].ctypes.data_as(_F64),
+                                    out["steps"].ctypes.data_as(_I64)))
+        return out
+
+    def _one(self, slot, shape, dtype, ctype):
+        a = np.zeros(shape, dtype)
+        args = [None] * 6
+        args[slot] = a.ctypes.data_as(ctype)
+        check(lib().orc_tracers_get(self.ptr, *args))
+        return a
+
+    positions = property(lambda self: self._one(0, (len(self), 3), np.float64, _F64))
+    cell = property(lambda self: self._one(1, len(self), np.int64, _I64))
+    status = property(lambda self: self._one(2, len(self), np.int32, _I32))
+    zone = property(lambda self: self._one(3, len(self), np.int32, _I32))
+    age = property(lambda self: self._one(4, len(self), np.float64, _F64))
+    steps = property(lambda self: self._one(5, len(self), np.int64, _I64))
+
+    @property
+    def active(self):
+        return self.status == 0
+
+
 class Mesh:
     """Device-resident mesh (OrcMesh*)."""
 
@@ -317,6 +367,11 @@ class Mesh:
     def probe_search_stats(self, reset=False):
         """the counters of the point search (module function probe_search_stats)"""
         return probe_search_stats(reset)
+
+    def seed(self, points):
+        """orc_tracers_create: tracer particles at the points [n, 3], located as locate() locates them -> Tracers.  Seeds outside the
+        mesh are LEFT from the start and never move."""
+        return Tracers(self, points)
 
     def matrix_pattern(self):
         rp = np.empty(self.n_cells + 1, np.int64)

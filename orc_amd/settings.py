@@ -217,3 +217,35 @@ class ProbeInterpolation:  # include/orc_types.h OrcProbeInterpolation
 
 
 PROBE_WALK_LIMIT = 64  # include/orc_types.h ORC_PROBE_WALK_LIMIT: moves of a walk
+
+
+class TracerStatus:  # include/orc_types.h OrcTracerStatus
+    ACTIVE, LEFT, WALK_LIMIT, STAGNANT = 0, 1, 2, 3
+
+
+class TracerScheme:  # include/orc_types.h OrcTracerScheme
+    EULER, RK2 = 0, 1
+
+
+class TracerStepMode:  # include/orc_types.h OrcTracerStepMode
+    TIME, LENGTH = 0, 1
+
+
+class TracerSettings(C.Structure):
+    """OrcTracerSettings: how Solver.advect moves a Mesh.seed() set — scheme (TracerScheme), interpolation (ProbeInterpolation),
+    step_mode (TracerStepMode: `step` is a time, or the length of a substep), direction (+1 with the flow, -1 against it), min_speed
+    (LENGTH: a particle slower than this becomes STAGNANT)."""
+    _fields_ = [("scheme", C.c_int32), ("interpolation", C.c_int32), ("step_mode", C.c_int32), ("direction", C.c_int32),
+                ("step", C.c_double), ("min_speed", C.c_double)]
+
+    @classmethod
+    def make(cls, step=0.0, **overrides):
+        """orc_tracer_settings_default (RK2, LINEAR, LENGTH, +1, min_speed 0) with the step and any other field overridden"""
+        s = cls()
+        lib().orc_tracer_settings_default(C.byref(s))
+        s.step = float(step)
+        for k, v in overrides.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s

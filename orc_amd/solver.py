@@ -706,6 +706,71 @@ class Solver:
         rows = {PROBE_NAMES[f]: np.ascontiguousarray(out[:, q, :n]) for q, f in enumerate(order)}
         return times, {name: rows[name] for name in names}
 
+    # ---------------------------------------------------------------- tracer particles (orc_solver_advect_tracers, ...)
+    def advect(self, tracers, settings, n_substeps, record_stride=0, raise_on_error=True):
+        """orc_solver_advect_tracers: up to n_substeps substeps of a Mesh.seed() set in the current u, v, w (settings.TracerSettings).
+        record_stride > 0 (a divisor of n_substeps) -> (path [K + 1, n, 3], path_len [n]): the positions after every record_stride
+        substeps, record 0 those at entry; the polyline of particle i is path[:path_len[i], i].  Otherwise None.  Reads the solver
+        only.  (raise_on_error=False: (status, result))"""
+        n = len(tracers) if tracers is not None else 0
+        path = plen = None
+        if record_stride > 0:
+            K = n_substeps // record_stride
+            path, plen = np.zeros((K + 1, 3, max(n, 1))), np.zeros(max(n, 1), np.int32)
+        st = lib().orc_solver_advect_tracers(self.ptr, tracers.ptr if tracers is not None else None, C.byref(settings) if settings is not None else None,
+                                             C.c_uint64(n_substeps), C.c_uint64(record_stride), None if path is None else _p(path),
+                                             None if plen is None else plen.ctypes.data_as(C.POINTER(C.c_int32)))
+        res = None
+        if st == 0 and path is not None:
+            res = (np.ascontiguousarray(path[:, :, :n].transpose(0, 2, 1)), plen[:n])
+        if raise_on_error:
+            check(st)
+            return res
+        return st, res
+
+    def streamlines(self, points, step, n_substeps, both_directions=False, **kw):
+        """Streamlines of the current velocity from the points [n, 3]: seeds, advects with LENGTH steps of `step` and a recorded path
+        -> a list of [m_i, 3] arrays.  both_directions joins the backward half (reversed) to the forward half at the seed.  kw:
+        further fields of settings.TracerSettings (scheme, interpolation, min_speed)."""
+        from .settings import TracerSettings, TracerStepMode
+        halves = []
+        for direction in ((-1, 1) if both_directions else (1,)):
+            c = TracerSettings.make(step, step_mode=TracerStepMode.LENGTH, direction=direction, **kw)
+            path, plen = self.advect(self.mesh.seed(points), c, n_substeps, record_stride=1)
+            halves.append([path[:plen[i], i] for i in range(path.shape[1])])
+        if not both_directions:
+            return halves[0]
+        return [np.concatenate([b[:0:-1], f]) for b, f in zip(*halves)]
+
+    def sample_tracers(self, tracers, fields=("u", "v", "w", "p"), interpolation="linear", raise_on_error=True):
+        """orc_solver_sample_tracers: sample() at the particles' present positions and cells -> {name: ndarray[len(tracers)]}"""
+        mask, names = _mask_of(fields, PROBE_NAMES)
+        out = np.zeros((max(bin(mask).count("1"), 1), len(tracers)))
+        st = lib().orc_solver_sample_tracers(self.ptr, tracers.ptr, C.c_uint32(mask & 0xFFFFFFFF), C.c_int32(_interpolation(interpolation)), _p(out))
+        res = _probe_rows(out, mask, names) if st == 0 else {}
+        if raise_on_error:
+            check(st)
+            return res
+        return st, res
+
+    def set_tracer_tracking(self, tracers=None, settings=None, substeps=1, raise_on_error=True):
+        """orc_solver_set_tracer_tracking: from now on every step of advance() moves the set by `substeps` substeps of dt / substeps in
+        the velocity just reached (TIME mode, direction +1; the settings' step is ignored); tracers=None turns it off.  Reads only:
+        fields and reports keep their bits, and a step gains no synchronisation."""
+        st = lib().orc_solver_set_tracer_tracking(self.ptr, tracers.ptr if tracers is not None else None,
+                                                  C.byref(settings) if settings is not None else None, C.c_uint32(substeps))
+        if st == 0:
+            self._tracked = tracers  # keeps the set alive while advance() moves it
+        if raise_on_error:
+            check(st)
+        return st
+
+    def bench_tracers(self, tracers, settings, n_substeps, reps=5):
+        """orc_bench_tracers: HIP-event ms per launch of n_substeps substeps from the set's state into scratch buffers"""
+        ms = C.c_double(0.0)
+        check(lib().orc_bench_tracers(self.ptr, tracers.ptr, C.byref(settings), C.c_uint64(n_substeps), C.c_int(reps), C.byref(ms)))
+        return ms.value
+
     def surface_report(self, origin=None, raise_on_error=True):
         """orc_solver_surface_report: per-zone force, moment, mass and momentum flow, area and mean pressure of the current
         state -> SurfaceReport (with raise_on_error=False: (status, report)); reads only"""
