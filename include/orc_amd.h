@@ -56,10 +56,18 @@ OrcMesh *orc_mesh_create(int64_t n_cells, int64_t n_faces, int32_t n_zones,
                          const int32_t *zone_type, const double *zone_scalar, const double *zone_vector /*[3Z]*/,
                          int *status);
 /* The same mesh with its cells renumbered internally by `ordering` (OrcCellOrdering; ORC_ORDER_RCM = the north star's
- * "rows sorted by RCM"): for meshes whose generator numbered the cells arbitrarily.  orc_solver_set_fields /
- * orc_solver_get_fields / orc_solve_steady keep taking and returning fields in ORC order; matrices, patterns and the
- * per-cell arrays of the assembly entry points are in the internal order, which orc_mesh_cell_order reports
- * (global_ids[c] = ORC index of internal cell c).  A renumbered run is the reference's algorithm on a renumbered mesh: its
+ * "rows sorted by RCM"): for meshes whose generator numbered the cells arbitrarily.  Callers keep speaking ORC order:
+ *   ORC order       every per-cell array of orc_solver_set_fields / get_fields, orc_solve_steady / _steady_converged / _transient,
+ *                   orc_solver_set_time_levels, orc_initialize_*, the scalar arm's field, source and levels, the viscosity arm's
+ *                   field, orc_solver_get_viscosity / evaluate_viscosity, orc_mesh_wall_distance, orc_derived_fields /
+ *                   orc_solver_derived_fields, the fields into orc_surface_integrals / orc_boundary_fields, the time statistics
+ *                   (get and set_statistics_state), and the cell ids of orc_probes_get / orc_tracers_get
+ *   internal order  matrices, patterns and the per-cell arrays of the assembly entry points (orc_mesh_matrix_pattern,
+ *                   orc_solver_assemble_momentum / _pressure / _scalar, orc_solver_get_diffusion, orc_solver_get_pressure_rhs,
+ *                   orc_build_momentum_diffusion_matrix, orc_initialize_momentum_matrix)
+ *   mixed           fields in in ORC order, results out in internal order: orc_calculate_gradients,
+ *                   orc_build_momentum_advection_matrices, orc_build_pressure_correction_matrices
+ * orc_mesh_cell_order reports the internal order (global_ids[c] = ORC index of internal cell c).  A renumbered run is the reference's algorithm on a renumbered mesh: its
  * iterates differ from the ORC-order run wherever the reference depends on the numbering (pairwise aggregation by row
  * index), its converged fields do not. */
 OrcMesh *orc_mesh_create_reordered(int64_t n_cells, int64_t n_faces, int32_t n_zones,

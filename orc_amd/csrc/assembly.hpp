@@ -94,7 +94,7 @@ struct OrcMesh {
     orc::SellMatrix pat;  // shared sparsity of a_di, a_u, a_v, a_w, A_p
     std::vector<int64_t> h_row_ptr, h_col;  // the same pattern in CSR (ORC order) for the C ABI
     std::vector<int64_t> h_global_ids;      // orc_mesh_create_reordered: ORC index of every internal cell (empty = identity);
-                                            // orc_solver_set_fields / get_fields / orc_solve_steady permute through it
+                                            // read by cell_order.hpp alone, which every per-cell array of the C ABI goes through
     std::unique_ptr<orc::SurfaceIndex> surface;  // null until the first surface report (surface.hip)
     std::unique_ptr<orc::WallDistance> wall;     // null until the first wall distance (wall_distance.hip)
     std::unique_ptr<orc::ProbeTiles> probe_tiles;  // null until the first probe set (probes.hip)

@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "assembly.hpp"
+#include "cell_order.hpp"
 #include "gradient_cell.hpp"
 
 
@@ -140,18 +141,6 @@ __global__ __launch_bounds__(kBlock) void boundary_map_k(MeshDev M, BoundaryArgs
 
 int popcount32(uint32_t m) { return __builtin_popcount(m); }
 
-// internal cell order on the device -> the caller's ORC order, field by field; entries past n_own were zeroed on the device
-int download_fields(const OrcMesh &m, const DevBuf<double> &dev, int k, double *out) {
-    const size_t n = (size_t)m.n_cells;
-    const std::vector<int64_t> &g = m.h_global_ids;
-    if (g.empty()) return dev.download(out, (size_t)k * n);
-    std::vector<double> tmp((size_t)k * n);
-    ORC_TRY(dev.download(tmp.data(), (size_t)k * n));
-    for (int q = 0; q < k; ++q)
-        for (size_t c = 0; c < n; ++c) out[(size_t)q * n + (size_t)g[c]] = tmp[(size_t)q * n + c];
-    return ORC_OK;
-}
-
 int fetch(DevBuf<int> &status, bool partitioned, const char *what) {
     int h = 0;
     ORC_TRY(status.download(&h, 1));
@@ -181,7 +170,7 @@ int derived_fields_dev(OrcMesh &m, double *u, double *v, double *w, const OrcSet
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(derived_cell_k<false>), dim3(grid), dim3(kBlock), 0, ctx().stream, m.dev(), A, status.p);
     ORC_HIP(hipGetLastError());
-    ORC_TRY(download_fields(m, dev, k, out));
+    ORC_TRY(download_cells(m, dev.p, out, k));  // entries past n_own were zeroed on the device
     return fetch(status, m.halo.active(), "derived fields");
 }
 
@@ -201,15 +190,6 @@ int boundary_fields_dev(OrcMesh &m, const double *u, const double *v, const doub
         ORC_TRY(dev.download(out, (size_t)k * (size_t)nb));
     }
     return fetch(status, m.halo.active(), "boundary fields");
-}
-
-int upload_in_internal_order(const OrcMesh &m, const double *src, DevBuf<double> &dst) {
-    const size_t n = (size_t)m.n_cells;
-    const std::vector<int64_t> &g = m.h_global_ids;  // reordered mesh: internal cell c holds ORC cell g[c]
-    if (g.empty()) return dst.upload(src, n);
-    std::vector<double> tmp(n);
-    for (size_t c = 0; c < n; ++c) tmp[c] = src[g[c]];
-    return dst.upload(tmp.data(), n);
 }
 
 }  // namespace
@@ -246,7 +226,7 @@ int orc_derived_fields(OrcMesh *m, const double *u, const double *v, const doubl
     if (mask == 0 || (mask >> ORC_DERIVED_N) != 0) return set_error(ORC_ERR_BAD_ARGUMENT, "derived fields: mask 0x%x selects nothing or an unknown field", mask);
     const double *src[3] = {u, v, w};
     DevBuf<double> dev[3];
-    for (int k = 0; k < 3; ++k) ORC_TRY(upload_in_internal_order(*m, src[k], dev[k]));
+    for (int k = 0; k < 3; ++k) ORC_TRY(upload_cells(*m, src[k], dev[k]));
     return derived_fields_dev(*m, dev[0].p, dev[1].p, dev[2].p, *settings, mask, out);
 }
 
@@ -267,7 +247,7 @@ int orc_boundary_fields(OrcMesh *m, const double *u, const double *v, const doub
         return set_error(ORC_ERR_BAD_ARGUMENT, "boundary fields: rho and mu must be positive and finite");
     const double *src[4] = {u, v, w, p};
     DevBuf<double> dev[4];
-    for (int k = 0; k < 4; ++k) ORC_TRY(upload_in_internal_order(*m, src[k], dev[k]));
+    for (int k = 0; k < 4; ++k) ORC_TRY(upload_cells(*m, src[k], dev[k]));
     return boundary_fields_dev(*m, dev[0].p, dev[1].p, dev[2].p, dev[3].p, rho, mu, nullptr, mask, out);
 }
 

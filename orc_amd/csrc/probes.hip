@@ -25,6 +25,7 @@
 #include <numeric>
 
 #include "assembly.hpp"
+#include "cell_order.hpp"
 #include "gradient_cell.hpp"
 #include "point_walk.hpp"
 #include "probes.hpp"
@@ -267,8 +268,8 @@ int ensure_tiles(OrcMesh &m) {
                            m.ccx.p, m.ccy.p, m.ccz.p, m.n_own, T->n_tiles, T->tiles.p);
         ORC_HIP(hipGetLastError());
     }
-    if (!m.h_global_ids.empty()) {
-        std::vector<int32_t> g(m.h_global_ids.begin(), m.h_global_ids.end());
+    if (!cell_order_ids(m).empty()) {
+        std::vector<int32_t> g(cell_order_ids(m).begin(), cell_order_ids(m).end());
         ORC_TRY(T->orc_id.upload(g.data(), g.size()));
     }
     ORC_HIP(hipStreamSynchronize(ctx().stream));
@@ -524,8 +525,7 @@ int orc_probes_get(const OrcProbes *p, int64_t *cell, int32_t *status, int32_t *
     std::vector<int32_t> h(n);
     if (cell) {
         ORC_TRY(p->cell.download(h.data(), n));
-        const std::vector<int64_t> &g = p->mesh->h_global_ids;  // reordered mesh: internal cell c holds ORC cell g[c]
-        for (size_t k = 0; k < n; ++k) cell[p->order[k]] = g.empty() ? (int64_t)h[k] : g[(size_t)h[k]];
+        for (size_t k = 0; k < n; ++k) cell[p->order[k]] = orc_cell_id(*p->mesh, h[k]);
     }
     const DevBuf<int32_t> *src[3] = {&p->status, &p->steps, &p->zone};
     int32_t *dst[3] = {status, steps, zone};

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "assembly.hpp"
+#include "cell_order.hpp"
 
 namespace orc {
 namespace {
@@ -401,15 +402,6 @@ int solve(SolverState &s, double report[4]) {
     return st;
 }
 
-int upload_orc_order(SolverState &s, DevBuf<double> &dst, const double *src) {
-    const size_t n = (size_t)s.n;
-    const std::vector<int64_t> &g = s.mesh->h_global_ids;
-    if (g.empty()) return dst.upload(src, n);
-    std::vector<double> tmp(n);
-    for (size_t i = 0; i < n; ++i) tmp[i] = src[g[i]];
-    return dst.upload(tmp.data(), n);
-}
-
 int validate(const OrcScalarSettings &c) {
     if (!(c.diffusivity > 0.) || !std::isfinite(c.diffusivity)) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: diffusivity must be positive and finite");
     if (!(c.scheme == ORC_MOMENTUM_UD || c.scheme == ORC_MOMENTUM_CD1 || scheme_is_tvd(c.scheme)))
@@ -513,20 +505,14 @@ int orc_solver_set_scalar_bc(OrcSolver *s, int32_t zone, int32_t kind, double va
 int orc_solver_set_scalar_field(OrcSolver *s, const double *phi) {
     if (!s || !phi) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
     if (!s->st.sc.on) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: the arm is off (orc_solver_set_scalar)");
-    return upload_orc_order(s->st, s->st.sc.phi, phi);
+    return upload_cells(*s->st.mesh, phi, s->st.sc.phi);
 }
 
 int orc_solver_get_scalar_field(OrcSolver *s, double *phi) {
     if (!s || !phi) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
     SolverState &st = s->st;
     if (!st.sc.on) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: the arm is off (orc_solver_set_scalar)");
-    const size_t n = (size_t)st.n;
-    const std::vector<int64_t> &g = st.mesh->h_global_ids;
-    if (g.empty()) return st.sc.phi.download(phi, n);
-    std::vector<double> tmp(n);
-    ORC_TRY(st.sc.phi.download(tmp.data(), n));
-    for (size_t i = 0; i < n; ++i) phi[g[i]] = tmp[i];
-    return ORC_OK;
+    return download_cells(*st.mesh, st.sc.phi.p, phi);
 }
 
 int orc_solver_set_scalar_source(OrcSolver *s, const double *source) {
@@ -534,7 +520,7 @@ int orc_solver_set_scalar_source(OrcSolver *s, const double *source) {
     SolverState &st = s->st;
     if (!st.sc.on) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: the arm is off (orc_solver_set_scalar)");
     if (!source) { st.sc.has_source = false; return ORC_OK; }
-    ORC_TRY(upload_orc_order(st, st.sc.src, source));
+    ORC_TRY(upload_cells(*st.mesh, source, st.sc.src));
     st.sc.has_source = true;
     return ORC_OK;
 }
@@ -545,8 +531,8 @@ int orc_solver_set_scalar_levels(OrcSolver *s, const double *phi_n, const double
     if (!st.sc.on) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: the arm is off (orc_solver_set_scalar)");
     if (!st.transient) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar levels without orc_solver_set_transient");
     if (!phi_n) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: level n must be given");
-    ORC_TRY(upload_orc_order(st, st.sc.lev[0], phi_n));
-    if (phi_nm1) ORC_TRY(upload_orc_order(st, st.sc.lev[1], phi_nm1));
+    ORC_TRY(upload_cells(*st.mesh, phi_n, st.sc.lev[0]));
+    if (phi_nm1) ORC_TRY(upload_cells(*st.mesh, phi_nm1, st.sc.lev[1]));
     st.sc.levels = phi_nm1 ? 2 : 1;
     return ORC_OK;
 }

@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "assembly.hpp"
+#include "cell_order.hpp"
 
 namespace orc {
 
@@ -324,17 +325,9 @@ int orc_surface_integrals(OrcMesh *m, const double *u, const double *v, const do
     if (origin && !finite3(origin)) return set_error(ORC_ERR_BAD_ARGUMENT, "surface integrals: the origin must be finite");
     if (!(rho > 0.) || !std::isfinite(rho) || !(mu > 0.) || !std::isfinite(mu))
         return set_error(ORC_ERR_BAD_ARGUMENT, "surface integrals: rho and mu must be positive and finite");
-    const size_t n = (size_t)m->n_cells;
-    const std::vector<int64_t> &g = m->h_global_ids;  // reordered mesh: internal cell c holds ORC cell g[c]
     const double *src[4] = {u, v, w, p};
     DevBuf<double> dev[4];
-    std::vector<double> tmp;
-    for (int k = 0; k < 4; ++k) {
-        if (g.empty()) { ORC_TRY(dev[k].upload(src[k], n)); continue; }
-        tmp.resize(n);
-        for (size_t c = 0; c < n; ++c) tmp[c] = src[k][g[c]];
-        ORC_TRY(dev[k].upload(tmp.data(), n));
-    }
+    for (int k = 0; k < 4; ++k) ORC_TRY(upload_cells(*m, src[k], dev[k]));
     return surface_report_dev(*m, dev[0].p, dev[1].p, dev[2].p, dev[3].p, rho, mu, nullptr, origin, per_zone);
 }
 

@@ -13,6 +13,7 @@
 #include <cstddef>
 
 #include "assembly.hpp"
+#include "cell_order.hpp"
 #include "gradient_cell.hpp"
 
 namespace orc {
@@ -278,18 +279,13 @@ int orc_solver_get_statistics(OrcSolver *s, uint32_t field_mask, int32_t form, d
     if (form != ORC_STAT_RAW && form != ORC_STAT_NORMALISED) return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: unknown form %d", form);
     if (form == ORC_STAT_NORMALISED && T.samples == 0) return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: NORMALISED needs at least one sample");
     const size_t n = (size_t)st.n;
-    const std::vector<int64_t> &g = st.mesh->h_global_ids;  // reordered mesh: internal cell c holds ORC cell g[c]
-    std::vector<double> tmp(g.empty() ? 0 : n);
     int slot = 0, q = 0;  // slot: row of the accumulator buffer; q: row of out
     for (int f = 0; f < ORC_STAT_N; ++f) {
         if (!(T.field_mask >> f & 1)) continue;
         const double *src = T.acc.p + (size_t)slot++ * n;
         if (!(field_mask >> f & 1)) continue;
         double *dst = out + (size_t)q++ * n;
-        if (n) ORC_HIP(hipMemcpyAsync(g.empty() ? dst : tmp.data(), src, n * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
-        ORC_HIP(hipStreamSynchronize(ctx().stream));
-        if (!g.empty())
-            for (size_t c = 0; c < n; ++c) dst[g[c]] = tmp[c];
+        ORC_TRY(download_cells(*st.mesh, src, dst));
         const bool mean = f <= ORC_STAT_P || f == ORC_STAT_MU || f == ORC_STAT_PHI;
         if (form == ORC_STAT_NORMALISED && !mean)
             for (size_t c = 0; c < n; ++c) dst[c] = dst[c] / T.W;
@@ -312,11 +308,10 @@ int orc_solver_set_statistics_state(OrcSolver *s, uint64_t samples, double weigh
     if (boundary != (boundary_means != nullptr))
         return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: boundary means are given exactly when the BOUNDARY group is on");
     const size_t n = (size_t)st.n, n_own = (size_t)st.n_own;
-    const std::vector<int64_t> &g = st.mesh->h_global_ids;
-    std::vector<double> tmp((size_t)T.n_fields * n);
-    for (int k = 0; k < T.n_fields; ++k)
-        for (size_t c = 0; c < n; ++c) tmp[(size_t)k * n + c] = c < n_own ? raw[(size_t)k * n + (g.empty() ? c : (size_t)g[c])] : 0.;  // ghost entries stay 0
-    if (!tmp.empty()) ORC_TRY(T.acc.upload(tmp.data(), tmp.size()));
+    std::vector<double> own;  // ghost entries stay 0: a partitioned mesh (never a reordered one) uploads a copy with them zeroed
+    if (n_own < n) own.assign(raw, raw + (size_t)T.n_fields * n);
+    for (size_t k = 0; k < (size_t)T.n_fields && n_own < n; ++k) std::fill(own.begin() + (k * n + n_own), own.begin() + (k + 1) * n, 0.);
+    ORC_TRY(upload_cells(*st.mesh, own.empty() ? raw : own.data(), T.acc, T.n_fields));
     if (boundary && T.nb > 0) ORC_TRY(T.bnd.upload(boundary_means, (size_t)ORC_STAT_BOUNDARY_N * (size_t)T.nb));
     T.W = weight_sum;
     T.samples = samples;

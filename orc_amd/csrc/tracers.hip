@@ -20,6 +20,7 @@
 #include <cmath>
 #include <memory>
 
+#include "cell_order.hpp"
 #include "gradient_cell.hpp"
 #include "point_walk.hpp"
 #include "probes.hpp"
@@ -285,8 +286,7 @@ int orc_tracers_get(const OrcTracers *t, double *xyz, int64_t *cell, int32_t *st
     std::vector<int32_t> h(n);
     if (cell) {
         ORC_TRY(s.cell.download(h.data(), n));
-        const std::vector<int64_t> &g = t->mesh->h_global_ids;  // reordered mesh: internal cell c holds ORC cell g[c]
-        for (size_t k = 0; k < n; ++k) cell[t->order[k]] = g.empty() ? (int64_t)h[k] : g[(size_t)h[k]];
+        for (size_t k = 0; k < n; ++k) cell[t->order[k]] = orc_cell_id(*t->mesh, h[k]);
     }
     if (status) { ORC_TRY(s.status.download(h.data(), n)); unsort(t->order, h.data(), status); }
     if (zone) { ORC_TRY(s.zone.download(h.data(), n)); unsort(t->order, h.data(), zone); }

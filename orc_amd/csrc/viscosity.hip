@@ -19,6 +19,7 @@
 #include <initializer_list>
 
 #include "assembly.hpp"
+#include "cell_order.hpp"
 #include "gradient_cell.hpp"
 
 namespace orc {
@@ -202,18 +203,6 @@ int status_of(SolverState &s, const char *what) {
     return ORC_OK;
 }
 
-int download_orc_order(const SolverState &s, const double *dev, double *dst) {
-    const size_t n = (size_t)s.n;
-    const std::vector<int64_t> &g = s.mesh->h_global_ids;  // reordered mesh: internal cell c holds ORC cell g[c]
-    std::vector<double> tmp;
-    double *host = g.empty() ? dst : (tmp.resize(n), tmp.data());
-    if (n) ORC_HIP(hipMemcpyAsync(host, dev, n * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
-    ORC_HIP(hipStreamSynchronize(ctx().stream));
-    if (!g.empty())
-        for (size_t c = 0; c < n; ++c) dst[g[c]] = tmp[c];
-    return ORC_OK;
-}
-
 }  // namespace
 
 int k_viscosity(SolverState &s, double *mu_out, double *g_out, bool relax) {
@@ -353,13 +342,7 @@ int orc_solver_set_viscosity_field(OrcSolver *s, const double *mu) {
     for (size_t i = 0; i < n; ++i)
         if (!(mu[i] > 0.) || !std::isfinite(mu[i]))
             return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity field: entry %lld is not positive and finite", (long long)i);
-    const std::vector<int64_t> &g = st.mesh->h_global_ids;
-    if (g.empty()) ORC_TRY(V.field.upload(mu, n));
-    else {
-        std::vector<double> tmp(n);
-        for (size_t c = 0; c < n; ++c) tmp[c] = mu[g[c]];
-        ORC_TRY(V.field.upload(tmp.data(), n));
-    }
+    ORC_TRY(upload_cells(*st.mesh, mu, V.field));
     V.has_field = true;
     if (V.on && V.c.model == ORC_VISCOSITY_FIELD) {
         ORC_TRY(vec_copy(V.mu.p, V.field.p, st.n));
@@ -377,7 +360,7 @@ int orc_solver_get_viscosity(OrcSolver *s, double *mu) {
         std::fill(mu, mu + st.n, st.mu);
         return ORC_OK;
     }
-    return download_orc_order(st, st.vis.mu.p, mu);
+    return download_cells(*st.mesh, st.vis.mu.p, mu);
 }
 
 int orc_solver_evaluate_viscosity(OrcSolver *s, double *mu, double *strain_rate) {
@@ -391,8 +374,8 @@ int orc_solver_evaluate_viscosity(OrcSolver *s, double *mu, double *strain_rate)
     ORC_TRY(g_t.alloc(n)); ORC_TRY(g_t.zero());
     ORC_TRY(exchange_velocities(st));
     ORC_TRY(k_viscosity(st, m_t.p, g_t.p, false));
-    ORC_TRY(download_orc_order(st, m_t.p, mu));
-    if (strain_rate) ORC_TRY(download_orc_order(st, g_t.p, strain_rate));
+    ORC_TRY(download_cells(*st.mesh, m_t.p, mu));
+    if (strain_rate) ORC_TRY(download_cells(*st.mesh, g_t.p, strain_rate));
     return status_of(st, "evaluate viscosity");
 }
 

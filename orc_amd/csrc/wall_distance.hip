@@ -23,6 +23,7 @@
 #include <initializer_list>
 
 #include "assembly.hpp"
+#include "cell_order.hpp"
 #include "sphere_cull.hpp"
 
 namespace orc {
@@ -269,18 +270,6 @@ int search(OrcMesh &m, const WallDistance &X, bool cull, double *d_dev, int laun
     return ORC_OK;
 }
 
-int download_orc_order(const OrcMesh &m, const double *dev, double *dst) {
-    const size_t n = (size_t)m.n_cells;
-    const std::vector<int64_t> &g = m.h_global_ids;  // reordered mesh: internal cell c holds ORC cell g[c]
-    std::vector<double> tmp;
-    double *host = g.empty() ? dst : (tmp.resize(n), tmp.data());
-    if (n) ORC_HIP(hipMemcpyAsync(host, dev, n * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
-    ORC_HIP(hipStreamSynchronize(ctx().stream));
-    if (!g.empty())
-        for (size_t c = 0; c < n; ++c) dst[g[c]] = tmp[c];
-    return ORC_OK;
-}
-
 // the mesh's cached field of `mask`, built and searched when the cache holds another mask or nothing
 int ensure_field(OrcMesh &m, const std::vector<int32_t> &mask, bool from_types) {
     if (m.wall && m.wall->searched && m.wall->mask == mask) {
@@ -352,7 +341,7 @@ int orc_mesh_wall_distance(OrcMesh *m, const int32_t *zone_is_wall, double *d) {
     std::vector<int32_t> mask;
     ORC_TRY(resolve_mask(*m, zone_is_wall, mask));
     ORC_TRY(ensure_field(*m, mask, zone_is_wall == nullptr));
-    return download_orc_order(*m, m->wall->d.p, d);
+    return download_cells(*m, m->wall->d.p, d);
 }
 
 int orc_debug_wall_distance(OrcMesh *m, const int32_t *zone_is_wall, int cull, double *d) {
@@ -364,7 +353,7 @@ int orc_debug_wall_distance(OrcMesh *m, const int32_t *zone_is_wall, int cull, d
     ORC_TRY(build_table(*m, mask, X));
     ORC_TRY(X.d.alloc((size_t)std::max<int64_t>(m->n_cells, 1)));
     ORC_TRY(search(*m, X, cull != 0, X.d.p, 1, nullptr));
-    return download_orc_order(*m, X.d.p, d);
+    return download_cells(*m, X.d.p, d);
 }
 
 int orc_debug_wall_search(long long out[5], int reset) {
