@@ -61,7 +61,8 @@ OrcMesh *orc_mesh_create(int64_t n_cells, int64_t n_faces, int32_t n_zones,
  *                   orc_solver_set_time_levels, orc_initialize_*, the scalar arm's field, source and levels, the viscosity arm's
  *                   field, orc_solver_get_viscosity / evaluate_viscosity, orc_mesh_wall_distance, orc_derived_fields /
  *                   orc_solver_derived_fields, the fields into orc_surface_integrals / orc_boundary_fields, the time statistics
- *                   (get and set_statistics_state), and the cell ids of orc_probes_get / orc_tracers_get
+ *                   (get and set_statistics_state), the cell ids of orc_probes_get / orc_tracers_get, and everything per cell of
+ *                   the volume reports (the labels and cell ids of a cell group set, the fields into orc_group_integrals, `where`)
  *   internal order  matrices, patterns and the per-cell arrays of the assembly entry points (orc_mesh_matrix_pattern,
  *                   orc_solver_assemble_momentum / _pressure / _scalar, orc_solver_get_diffusion, orc_solver_get_pressure_rhs,
  *                   orc_build_momentum_diffusion_matrix, orc_initialize_momentum_matrix)
@@ -663,6 +664,53 @@ int orc_solver_probe_history(OrcSolver *s, uint64_t first, uint64_t count, doubl
 OrcProbes *orc_debug_probes_locate(OrcMesh *m, int64_t n_points, const double *xyz, int cull, int slabs /*0 = automatic*/, int *status);
 int orc_debug_probe_search(long long out[6], int reset);
 int orc_bench_probe_locate(OrcMesh *m, const OrcProbes *p, int cull, int reps, double avg_ms[2]);
+
+/* ---------- volume reports (new-build extension, orc_types.h OrcGroupQuantity / OrcGroupWeighting) ----------
+ * A cell group set is a labelling of the cells of one mesh: group_of_cell[c] in [0, n_groups) for ORC cell c, or -1 for "in no group".
+ * A report reduces cell fields over every group on the device (orc_types.h, DESIGN.md §3 "Volume reports": definitions, operator order,
+ * association): sums[G][F][ORC_GROUP_N], weight[G][2] = (W, number of cells) and where[G][F][2] = the ORC ids of the cells of MIN and
+ * MAX; each output may be NULL.  Sums are deterministic (no float atomics) and depend on the group set only, not on the mesh's internal
+ * numbering.  Opt-in and read-only: no entry changes a bit of a mesh or a solver, and a solver without a group history launches what it
+ * launched before.
+ *  - orc_cell_groups_create: built once on the host and uploaded; NULL + *status on failure.  Destroy a set before its mesh, and after
+ *    any solver whose group history reads it.  A partitioned mesh is refused.
+ *  - orc_cell_groups_get: group_ptr[G + 1] into cells, cells[group_ptr[G]] the ORC ids ascending inside a group, *chunk the list entries
+ *    one workgroup of a report takes; each may be NULL.  orc_group_limits: the fields of one launch (more run in batches), that chunk,
+ *    the entries of one lane, the largest n_groups.
+ *  - orc_solver_group_report: the solver's current fields of field_mask (OrcProbeField bits, ascending; PHI needs the scalar arm, MU is
+ *    the constant while the viscosity arm is off).
+ *  - orc_group_integrals: n_fields caller fields, field k at fields[k * n_cells + c], ORC order.
+ *  - orc_solver_group_statistics: the running statistics of stat_field_mask (OrcStatField bits) in `form` (OrcStatForm), reduced where
+ *    they lie: per cell exactly the value orc_solver_get_statistics returns.
+ *  - orc_solver_set_group_history: g == NULL turns the history off and drops it; otherwise from now on orc_solver_advance appends one
+ *    report of field_mask after every step whose counter (steps since enabling, first = 1) is a multiple of `interval`, with the time
+ *    reached.  Reduced on the device after the step's other arms and copied asynchronously: no synchronisation is added to a step.
+ *  - orc_solver_record_groups: appends one record of the current state with `tag` in the time slot (steady runs).
+ *  - orc_solver_group_history_count / orc_solver_group_history: the records [first, first + count): times[count],
+ *    sums[count][G][F][ORC_GROUP_N], weight[G][2], where[count][G][F][2]; each may be NULL.
+ *  - orc_bench_group_report: HIP-event average ms over `reps` of avg_ms[0] group_chunk_k and avg_ms[1] group_fold_k on the solver's
+ *    fields of field_mask (at most one launch's fields).
+ * Every entry but orc_cell_groups_get / _count / orc_group_limits looks for a device first.  Refused with ORC_ERR_BAD_ARGUMENT, nothing
+ * changed: a null mesh, solver, label or field array; n_groups outside [1, ORC_GROUP_MAX_GROUPS]; a label outside [-1, n_groups); a
+ * partitioned mesh; a group set of another mesh; a field_mask of 0 or with unknown bits; ORC_PROBE_PHI without the scalar arm; n_fields
+ * outside [1, ORC_GROUP_MAX_FIELDS]; an unknown weighting; what orc_solver_get_statistics refuses; interval 0; orc_solver_record_groups
+ * and the history read-outs while the history is off; a range past the history. */
+typedef struct OrcCellGroups OrcCellGroups;
+OrcCellGroups *orc_cell_groups_create(OrcMesh *m, int32_t n_groups, const int32_t *group_of_cell /*[n_cells] ORC order*/, int *status);
+void orc_cell_groups_destroy(OrcCellGroups *g);
+int32_t orc_cell_groups_count(const OrcCellGroups *g);
+int orc_cell_groups_get(const OrcCellGroups *g, int64_t *group_ptr /*[G + 1]*/, int64_t *cells /*[group_ptr[G]] ORC ids*/, int32_t *chunk);
+int orc_group_limits(int32_t *fields_per_launch, int32_t *chunk, int32_t *lane_slots, int32_t *max_groups);
+int orc_solver_group_report(OrcSolver *s, OrcCellGroups *g, uint32_t field_mask, int32_t weighting, double *sums, double *weight, int64_t *where);
+int orc_group_integrals(OrcMesh *m, OrcCellGroups *g, int32_t n_fields, const double *fields /*[n_fields][n_cells] ORC order*/, int32_t weighting,
+                        double *sums, double *weight, int64_t *where);
+int orc_solver_group_statistics(OrcSolver *s, OrcCellGroups *g, uint32_t stat_field_mask, int32_t form, int32_t weighting, double *sums,
+                                double *weight, int64_t *where);
+int orc_solver_set_group_history(OrcSolver *s, OrcCellGroups *g /*NULL = off*/, uint32_t field_mask, int32_t weighting, uint64_t interval);
+int orc_solver_record_groups(OrcSolver *s, double tag);
+int64_t orc_solver_group_history_count(OrcSolver *s);
+int orc_solver_group_history(OrcSolver *s, uint64_t first, uint64_t count, double *times, double *sums, double *weight, int64_t *where);
+int orc_bench_group_report(OrcSolver *s, OrcCellGroups *g, uint32_t field_mask, int32_t weighting, int reps, double avg_ms[2]);
 
 /* ---------- tracer particles (new-build extension, orc_types.h OrcTracerStatus / OrcTracerSettings) ----------
  * A tracer set is a list of massless particles in the cells of one mesh, kept on the device: per particle the position, the cell, the

@@ -367,6 +367,19 @@ enum OrcProbeInterpolation {
                             gradient_reconstruction (a row of orc_calculate_gradients, bit for bit), r = x - x_P; PHI and MU: the cell's */
 };
 
+/* Volume reports (new-build extension; orc_amd.h: orc_cell_groups_create, orc_solver_group_report): per group g of a cell group set and
+ * per field x, with the weight w of a cell, t1 = w * x and t2 = t1 * x (separate multiplies): SUM = sum t1, SUM_SQ = sum t2, MIN, MAX
+ * and the cells where the extrema occur; per group W = sum w and the number of cells.  A NaN never wins a comparison; among equal
+ * values the smallest ORC cell id wins; a group without a cell, or with NaN only, gives +inf, -inf and the cell -1.  DESIGN.md §3
+ * "Volume reports" fixes the association of the sums. */
+enum OrcGroupQuantity { ORC_GROUP_SUM = 0, ORC_GROUP_SUM_SQ = 1, ORC_GROUP_MIN = 2, ORC_GROUP_MAX = 3, ORC_GROUP_N /* 4 */ };
+enum OrcGroupWeighting {
+    ORC_GROUP_WEIGHT_VOLUME = 0, /* w = the mesh's stored cell volume */
+    ORC_GROUP_WEIGHT_UNIT = 1    /* w = 1.0 */
+};
+#define ORC_GROUP_MAX_GROUPS (1 << 20) /* groups of one set */
+#define ORC_GROUP_MAX_FIELDS 64        /* fields of one orc_group_integrals call */
+
 /* Tracer particles (new-build extension; orc_amd.h: orc_tracers_create, orc_solver_advect_tracers): massless particles moved through
  * the cells in the solver's velocity.  A substep of an ACTIVE particle at (x, P): U1 = velocity(x, P); h = direction step (TIME) or
  * (direction step) / |U1| (LENGTH; STAGNANT unless |U1| > min_speed); EULER xn = x + h U1, RK2 xm = x + (0.5 h) U1, U2 at xm in the

@@ -202,6 +202,35 @@ def lib():
             L.orc_write_vtu_lines.restype = C.c_int
             L.orc_bench_tracers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, _f64]
             L.orc_bench_tracers.restype = C.c_int
+        # volume reports (orc_amd.h "volume reports"): full signatures
+        if hasattr(L, "orc_cell_groups_create"):
+            _f64, _i64, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+            L.orc_cell_groups_create.argtypes = [C.c_void_p, C.c_int32, _i32, C.POINTER(C.c_int)]
+            L.orc_cell_groups_create.restype = C.c_void_p
+            L.orc_cell_groups_destroy.argtypes = [C.c_void_p]
+            L.orc_cell_groups_destroy.restype = None
+            L.orc_cell_groups_count.argtypes = [C.c_void_p]
+            L.orc_cell_groups_count.restype = C.c_int32
+            L.orc_cell_groups_get.argtypes = [C.c_void_p, _i64, _i64, _i32]
+            L.orc_cell_groups_get.restype = C.c_int
+            L.orc_group_limits.argtypes = [_i32, _i32, _i32, _i32]
+            L.orc_group_limits.restype = C.c_int
+            L.orc_solver_group_report.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, _f64, _f64, _i64]
+            L.orc_solver_group_report.restype = C.c_int
+            L.orc_group_integrals.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, _f64, C.c_int32, _f64, _f64, _i64]
+            L.orc_group_integrals.restype = C.c_int
+            L.orc_solver_group_statistics.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, _f64, _f64, _i64]
+            L.orc_solver_group_statistics.restype = C.c_int
+            L.orc_solver_set_group_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_uint64]
+            L.orc_solver_set_group_history.restype = C.c_int
+            L.orc_solver_record_groups.argtypes = [C.c_void_p, C.c_double]
+            L.orc_solver_record_groups.restype = C.c_int
+            L.orc_solver_group_history_count.argtypes = [C.c_void_p]
+            L.orc_solver_group_history_count.restype = C.c_int64
+            L.orc_solver_group_history.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, _f64, _f64, _f64, _i64]
+            L.orc_solver_group_history.restype = C.c_int
+            L.orc_bench_group_report.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int, _f64]
+            L.orc_bench_group_report.restype = C.c_int
         # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
         if hasattr(L, "orc_debug_amg_setup_stats"):
             L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]

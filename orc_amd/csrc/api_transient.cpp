@@ -29,6 +29,7 @@ int advance_one(SolverState &st, double *row /*10*/) {
     ORC_TRY(stats_step_dev(st));   // statistics arm on: the step is counted and, when due, sampled with weight dt
     ORC_TRY(probes_step_dev(st));  // probe history on: the step is counted and, when due, recorded at the time reached
     ORC_TRY(tracers_step_dev(st)); // tracer tracking on: the set moves through the velocity just reached
+    ORC_TRY(groups_step_dev(st));  // group history on: the step is counted and, when due, reduced over the groups at the time reached
     if (row) {
         std::copy(rep, rep + 8, row);
         row[8] = (double)used;

@@ -293,6 +293,36 @@ struct SolverState {
             times.clear(); values.clear();
         }
     } ph;
+    // Group history (orc_solver_set_group_history, groups.hip): off unless enabled.  The probe history's scheme: a record [G][1 + 6 F] is
+    // reduced on the device into `rec`, copied to the pinned `raw` behind it and marked by `copied`; it joins the history at the next
+    // step, at a history call or when the arm goes off.  Reads the fields, never writes them; snapshot / restore leave it alone.
+    struct GroupHistory {
+        bool on = false;
+        OrcCellGroups *groups = nullptr;
+        uint32_t mask = 0;
+        int32_t weighting = 0;
+        int n_fields = 0;
+        uint64_t interval = 1, step = 0;  // orc_solver_advance steps since the arm was enabled
+        DevBuf<double> rec;               // one record as group_fold_k writes it
+        double *raw = nullptr;            // the same, pinned
+        hipEvent_t copied = nullptr;
+        bool pending = false;             // raw is on its way
+        double pending_time = 0.;
+        std::vector<double> w_of;         // [G] the weight sums W: the group set's and the weighting's, the same in every record
+        std::vector<double> times, values;  // k records: the time slots, and k records as the device wrote them
+        GroupHistory() = default;
+        GroupHistory(const GroupHistory &) = delete;
+        GroupHistory &operator=(const GroupHistory &) = delete;
+        ~GroupHistory() { clear(); }
+        void clear() {
+            if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
+            if (raw) (void)hipHostFree(raw);
+            copied = nullptr; raw = nullptr;
+            rec.release();
+            on = false; pending = false; groups = nullptr; mask = 0; n_fields = 0; step = 0;
+            w_of.clear(); times.clear(); values.clear();
+        }
+    } gh;
     // Tracer tracking (orc_solver_set_tracer_tracking, tracers.hip): off unless enabled.  Every step of orc_solver_advance moves the set
     // by `substeps` substeps of h in the new velocity; the kernel's status word is copied to the pinned `raw` behind it and looked at
     // by the next step.  Reads the fields, never writes them; snapshot / restore leave the set alone.
@@ -420,6 +450,9 @@ int probes_step_dev(SolverState &s);
 // tracer tracking (tracers.hip): what orc_solver_advance runs after probes_step_dev — while tracking is on, one launch that moves the
 // set through the step's velocity; asynchronous on ctx().stream, nothing while it is off
 int tracers_step_dev(SolverState &s);
+// group history (groups.hip): what orc_solver_advance runs last — counts the step and, when the history is on and the step is due,
+// reduces one record on the device and starts its copy to the host; asynchronous on ctx().stream, nothing while it is off
+int groups_step_dev(SolverState &s);
 
 }  // namespace orc
 

@@ -9,6 +9,13 @@ int64_t orc_cell_id(const OrcMesh &m, int32_t internal) {
     return m.h_global_ids.empty() ? (int64_t)internal : m.h_global_ids[(size_t)internal];
 }
 
+std::vector<int32_t> internal_cell_ids(const OrcMesh &m) {
+    const std::vector<int64_t> &g = m.h_global_ids;
+    std::vector<int32_t> inv(g.size());
+    for (size_t c = 0; c < g.size(); ++c) inv[(size_t)g[c]] = (int32_t)c;
+    return inv;
+}
+
 int upload_cells(const OrcMesh &m, const double *src_orc, DevBuf<double> &dst, int fields) {
     const size_t n = (size_t)m.n_cells, total = (size_t)fields * n;
     const std::vector<int64_t> &g = m.h_global_ids;

@@ -8,8 +8,10 @@
 //             set_scalar_source / set_scalar_levels, orc_solver_set_viscosity_field / get_viscosity / evaluate_viscosity,
 //             orc_mesh_wall_distance, orc_debug_wall_distance, orc_derived_fields, orc_solver_derived_fields, the fields into
 //             orc_surface_integrals and orc_boundary_fields, orc_solver_get_statistics / set_statistics_state, and the cell ids of
-//             orc_probes_get and orc_tracers_get
-//   internal  orc_mesh_matrix_pattern, the matrix values and right-hand sides of orc_solver_assemble_momentum / _pressure / _scalar,
+//             orc_probes_get and orc_tracers_get, the labels into orc_cell_groups_create, the cell ids of orc_cell_groups_get, the
+//             fields into orc_group_integrals and the `where` cells of every group report (orc_solver_group_report / _statistics /
+//             _history, orc_group_integrals)
+//   internalorc_mesh_matrix_pattern, the matrix values and right-hand sides of orc_solver_assemble_momentum / _pressure / _scalar,
 //             orc_solver_get_diffusion, orc_solver_get_pressure_rhs, orc_build_momentum_diffusion_matrix, orc_initialize_momentum_matrix
 //             (orc_mesh_cell_order reports g)
 //   mixed     fields in in ORC order, per-cell results out in internal order: orc_calculate_gradients,
@@ -23,6 +25,8 @@ namespace orc {
 const std::vector<int64_t> &cell_order_ids(const OrcMesh &m);
 // the ORC id of internal cell `internal`
 int64_t orc_cell_id(const OrcMesh &m, int32_t internal);
+// the inverse of g: the internal cell of every ORC id (empty = identity): groups.hip stores its ORC-ordered lists through it
+std::vector<int32_t> internal_cell_ids(const OrcMesh &m);
 // `fields` arrays of n = m.n_cells doubles, one after the other.  upload: dst[q n + c] = src_orc[q n + g[c]] (dst grows if need be);
 // download: dst_orc[q n + g[c]] = dev[q n + c].  Both copy on ctx().stream and return with it synchronised, as DevBuf::upload /
 // download do; the identity is a straight copy without a temporary.

@@ -221,6 +221,93 @@ class Probes:
         return float(ms[0]), float(ms[1])
 
 
+def group_limits():
+    """orc_group_limits -> dict(fields, chunk, slots, max_groups): the fields one launch of a volume report takes (more run in
+    batches), the list entries of one workgroup and of one lane, the largest n_groups.  Needs no device."""
+    v = [C.c_int32(0) for _ in range(4)]
+    check(lib().orc_group_limits(*[C.byref(x) for x in v]))
+    return dict(zip(("fields", "chunk", "slots", "max_groups"), (int(x.value) for x in v)))
+
+
+def bin_ids(cell_centroid, direction, edges):
+    """The labels of Mesh.bin_cells: s = (c.x d.x + c.y d.y) + c.z d.z with d = direction / |direction|, in float64 numpy; bin k holds the
+    cells with edges[k] <= s < edges[k + 1] (the lower edge belongs to the bin, the upper one to the next); a cell below edges[0], at or
+    above edges[-1], or with s NaN gets -1.  edges must ascend strictly.  -> (ids int32 [n], number of bins)"""
+    c = np.asarray(cell_centroid, dtype=np.float64).reshape(-1, 3)
+    d = np.asarray(direction, dtype=np.float64).reshape(3)
+    e = np.asarray(edges, dtype=np.float64).reshape(-1)
+    norm = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+    if not np.isfinite(norm) or norm == 0.0:
+        raise ValueError("bin_cells: the direction must be finite and not zero")
+    if len(e) < 2 or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+        raise ValueError("bin_cells: at least two finite, strictly ascending edges")
+    d = d / norm
+    s = (c[:, 0] * d[0] + c[:, 1] * d[1]) + c[:, 2] * d[2]
+    k = np.searchsorted(e, s, side="right") - 1
+    k[(k >= len(e) - 1) | np.isnan(s)] = -1
+    return k.astype(np.int32), len(e) - 1
+
+
+def box_ids(cell_centroid, lo, hi):
+    """The labels of Mesh.box_cells: 0 where lo[k] <= centroid[k] < hi[k] in every coordinate k, else -1 -> ids int32 [n]"""
+    c = np.asarray(cell_centroid, dtype=np.float64).reshape(-1, 3)
+    lo, hi = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+    inside = np.all((c >= lo[None, :]) & (c < hi[None, :]), axis=1)
+    return np.where(inside, 0, -1).astype(np.int32)
+
+
+def check_group_ids(ids, n_cells, n_groups=None):
+    """ids as orc_cell_groups_create takes them (int32 [n_cells], -1 = in no group) and n_groups (None: the largest id + 1, at least 1);
+    raises ValueError for what the library would refuse"""
+    a = np.asarray(ids)
+    if a.ndim != 1 or len(a) != n_cells:
+        raise ValueError("cell groups: one id per cell (%d), got shape %s" % (n_cells, a.shape))
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("cell groups: the ids must be integers")
+    if n_groups is None:
+        n_groups = max(int(a.max()) + 1, 1) if len(a) else 1
+    n_groups = int(n_groups)
+    if n_groups < 1:
+        raise ValueError("cell groups: n_groups must be at least 1")
+    if len(a) and (int(a.min()) < -1 or int(a.max()) >= n_groups):
+        raise ValueError("cell groups: an id lies outside [-1, %d)" % n_groups)
+    return np.ascontiguousarray(a, dtype=np.int32), n_groups
+
+
+class CellGroups:
+    """A labelling of the cells of a mesh (OrcCellGroups*), kept on the device as lists: what the volume reports reduce over.
+    len() = the groups; group_ptr [G + 1] into cells; cells = the ORC ids, ascending inside a group; chunk = the list entries one
+    workgroup of a report takes."""
+
+    def __init__(self, mesh, ids, n_groups=None):
+        self.mesh = mesh  # keeps the mesh alive: a group set goes before its mesh
+        self.ids, n_groups = check_group_ids(ids, mesh.n_cells, n_groups)
+        st = C.c_int(0)
+        ptr = lib().orc_cell_groups_create(mesh.ptr, C.c_int32(n_groups), self.ids.ctypes.data_as(_I32), C.byref(st))
+        check(st.value)
+        self.ptr = C.c_void_p(ptr)
+        self.group_ptr = np.zeros(n_groups + 1, np.int64)
+        chunk = C.c_int32(0)
+        check(lib().orc_cell_groups_get(self.ptr, self.group_ptr.ctypes.data_as(_I64), None, C.byref(chunk)))
+        self.cells = np.zeros(max(int(self.group_ptr[-1]), 1), np.int64)
+        check(lib().orc_cell_groups_get(self.ptr, None, self.cells.ctypes.data_as(_I64), None))
+        self.cells = self.cells[:int(self.group_ptr[-1])]
+        self.chunk = int(chunk.value)
+
+    def __del__(self):
+        if getattr(self, "ptr", None):
+            lib().orc_cell_groups_destroy(self.ptr)
+            self.ptr = None
+
+    def __len__(self):
+        return int(lib().orc_cell_groups_count(self.ptr))
+
+    @property
+    def count(self):
+        """cells per group"""
+        return np.diff(self.group_ptr)
+
+
 class Tracers:
     """Tracer particles in the cells of a mesh (OrcTracers*), kept on the device: what Solver.advect moves and Solver.sample_tracers
     reads.  positions [n, 3], cell (ORC order), status (settings.TracerStatus), zone (of the boundary face a LEFT particle went
@@ -367,6 +454,21 @@ class Mesh:
     def probe_search_stats(self, reset=False):
         """the counters of the point search (module function probe_search_stats)"""
         return probe_search_stats(reset)
+
+    def cell_groups(self, ids, n_groups=None):
+        """orc_cell_groups_create: ids[c] = the group of ORC cell c in [0, n_groups), -1 = in no group (n_groups=None: the largest
+        id + 1) -> CellGroups, what Solver.group_report and its relatives reduce over.  A partitioned mesh is refused."""
+        return CellGroups(self, ids, n_groups)
+
+    def bin_cells(self, direction, edges):
+        """Bins along a direction -> CellGroups with len(edges) - 1 groups.  The rule (bin_ids): s = centroid . direction / |direction|
+        in numpy; bin k holds edges[k] <= s < edges[k + 1]; a cell outside [edges[0], edges[-1]) is in no group."""
+        ids, n = bin_ids(self.arrays["cell_centroid"], direction, edges)
+        return CellGroups(self, ids, n)
+
+    def box_cells(self, lo, hi):
+        """The cells whose centroid lies in the box lo <= x < hi (per coordinate, box_ids) -> a CellGroups of one group"""
+        return CellGroups(self, box_ids(self.arrays["cell_centroid"], lo, hi), 1)
 
     def seed(self, points):
         """orc_tracers_create: tracer particles at the points [n, 3], located as locate() locates them -> Tracers.  Seeds outside the

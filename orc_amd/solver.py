@@ -278,6 +278,88 @@ def _probe_rows(out, mask, names):
     return {name: rows[name] for name in names}
 
 
+_I64 = C.POINTER(C.c_int64)
+_GROUP_N = 4  # orc_types.h ORC_GROUP_N: SUM, SUM_SQ, MIN, MAX
+GROUP_WEIGHTINGS = ("volume", "unit")  # orc_types.h OrcGroupWeighting, by value
+
+
+def _weighting(x):
+    """'volume' / 'unit' or an OrcGroupWeighting value -> the value"""
+    if isinstance(x, str):
+        if x.lower() not in GROUP_WEIGHTINGS:
+            raise KeyError("unknown weighting '%s'; known: %s" % (x, ", ".join(GROUP_WEIGHTINGS)))
+        return GROUP_WEIGHTINGS.index(x.lower())
+    return int(x)
+
+
+def _group_out(G, F):
+    return np.zeros((max(G, 1), max(F, 1), _GROUP_N)), np.zeros((max(G, 1), 2)), np.zeros((max(G, 1), max(F, 1), 2), np.int64)
+
+
+class GroupReport:
+    """A volume report (orc_solver_group_report and its relatives): per group g and field f (`names`, the columns)
+        weight [G] = W = sum w, count [G]; sum [G, F] = sum (w x), sum_sq = sum ((w x) x), min, max, argmin, argmax (ORC cell ids, -1
+        where the group holds no cell or NaN only)
+    and derived on the host: mean = sum / W, variance = sum_sq / W - mean^2, rms = sqrt(sum_sq / W); NaN where W is 0."""
+
+    def __init__(self, names, sums, weight, where):
+        self.names = list(names)
+        G, F = np.asarray(weight).reshape(-1, 2).shape[0], len(self.names)
+        self.raw = np.asarray(sums, dtype=np.float64).reshape(G, -1, _GROUP_N)[:, :F]
+        self.where = np.asarray(where, dtype=np.int64).reshape(G, -1, 2)[:, :F]
+        w = np.asarray(weight, dtype=np.float64).reshape(G, 2)
+        self.weight, self.count = w[:, 0].copy(), w[:, 1].astype(np.int64)
+
+    sum = property(lambda self: self.raw[:, :, 0])
+    sum_sq = property(lambda self: self.raw[:, :, 1])
+    min = property(lambda self: self.raw[:, :, 2])
+    max = property(lambda self: self.raw[:, :, 3])
+    argmin = property(lambda self: self.where[:, :, 0])
+    argmax = property(lambda self: self.where[:, :, 1])
+
+    def _per_weight(self, a):
+        out = np.full(a.shape, np.nan)
+        w = np.broadcast_to(self.weight[:, None], a.shape)
+        np.divide(a, w, out=out, where=w != 0.0)
+        return out
+
+    @property
+    def mean(self):
+        return self._per_weight(self.sum)
+
+    @property
+    def variance(self):
+        m = self.mean
+        return self._per_weight(self.sum_sq) - m * m
+
+    @property
+    def rms(self):
+        q = self._per_weight(self.sum_sq)
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(q)
+
+    def column(self, name):
+        """the column index of the field called `name`"""
+        return self.names.index(name)
+
+
+def group_integrals(mesh, groups, fields, weighting="volume", raise_on_error=True):
+    """orc_group_integrals: the volume report of caller fields {name: ndarray[n_cells]} in ORC cell order (a file's data, derived
+    fields, a product of two fields) -> GroupReport, columns in the dict's order (raise_on_error=False: (status, report or None))"""
+    names = list(fields.keys())
+    block = np.ascontiguousarray(np.stack([_f64(fields[k]).reshape(-1) for k in names]) if names else np.zeros((0, mesh.n_cells)))
+    if block.shape[1] != mesh.n_cells:
+        raise ValueError("group integrals: a field holds %d values, the mesh %d cells" % (block.shape[1], mesh.n_cells))
+    G = len(groups) if groups is not None else 0
+    sums, weight, where = _group_out(G, len(names))
+    st = lib().orc_group_integrals(mesh.ptr, groups.ptr if groups is not None else None, C.c_int32(len(names)), _p(block),
+                                   C.c_int32(_weighting(weighting)), _p(sums), _p(weight), where.ctypes.data_as(_I64))
+    if raise_on_error:
+        check(st)
+        return GroupReport(names, sums, weight, where)
+    return st, (GroupReport(names, sums, weight, where) if st == 0 else None)
+
+
 class Solver:
     """Device-resident state of one solve_steady call (OrcSolver*): what bench.py drives."""
 
@@ -705,6 +787,93 @@ class Solver:
         order = [i for i in range(len(PROBE_NAMES)) if mask >> i & 1]
         rows = {PROBE_NAMES[f]: np.ascontiguousarray(out[:, q, :n]) for q, f in enumerate(order)}
         return times, {name: rows[name] for name in names}
+
+    # ---------------------------------------------------------------- volume reports (orc_solver_group_report, ...)
+    def group_report(self, groups, fields=("u", "v", "w", "p"), weighting="volume", raise_on_error=True):
+        """orc_solver_group_report: the current fields (PROBE_NAMES or a bit mask; columns in PROBE_NAMES order) reduced over every group
+        of a Mesh.cell_groups() / bin_cells() / box_cells() set on the device -> GroupReport.  Reads only.  (raise_on_error=False:
+        (status, report or None))"""
+        mask, _ = _mask_of(fields, PROBE_NAMES)
+        names = [n for k, n in enumerate(PROBE_NAMES) if mask >> k & 1]
+        G = len(groups) if groups is not None else 0
+        sums, weight, where = _group_out(G, len(names))
+        st = lib().orc_solver_group_report(self.ptr, groups.ptr if groups is not None else None, C.c_uint32(mask & 0xFFFFFFFF),
+                                           C.c_int32(_weighting(weighting)), _p(sums), _p(weight), where.ctypes.data_as(_I64))
+        if raise_on_error:
+            check(st)
+            return GroupReport(names, sums, weight, where)
+        return st, (GroupReport(names, sums, weight, where) if st == 0 else None)
+
+    def group_statistics(self, groups, names=None, form="normalised", weighting="volume", raise_on_error=True):
+        """orc_solver_group_statistics: the running statistics `names` (STATISTIC_NAMES or a bit mask; None = every enabled field;
+        columns in STATISTIC_NAMES order) reduced over the groups where they lie, per cell exactly the values statistics() returns in
+        that form ('normalised' or 'raw') -> GroupReport.  (raise_on_error=False: (status, report or None))"""
+        if names is None:
+            names = self.statistics_fields()
+        mask, _ = _mask_of(names, STATISTIC_NAMES)
+        cols = [n for k, n in enumerate(STATISTIC_NAMES) if mask >> k & 1]
+        G = len(groups) if groups is not None else 0
+        sums, weight, where = _group_out(G, len(cols))
+        f = {"raw": 0, "normalised": 1}[form.lower()] if isinstance(form, str) else int(form)
+        st = lib().orc_solver_group_statistics(self.ptr, groups.ptr if groups is not None else None, C.c_uint32(mask & 0xFFFFFFFF), C.c_int32(f),
+                                               C.c_int32(_weighting(weighting)), _p(sums), _p(weight), where.ctypes.data_as(_I64))
+        if raise_on_error:
+            check(st)
+            return GroupReport(cols, sums, weight, where)
+        return st, (GroupReport(cols, sums, weight, where) if st == 0 else None)
+
+    def set_group_history(self, groups=None, fields=("u", "v", "w", "p"), interval=1, weighting="volume", raise_on_error=True):
+        """orc_solver_set_group_history: from now on advance() appends one group report of the fields after every `interval`-th step
+        (steps counted from 1 since enabling); groups=None turns the history off and drops it.  Reads only, and adds no
+        synchronisation to a step."""
+        if groups is None:
+            st = lib().orc_solver_set_group_history(self.ptr, None, C.c_uint32(0), C.c_int32(0), C.c_uint64(1))
+            names = []
+        else:
+            mask, _ = _mask_of(fields, PROBE_NAMES)
+            names = [n for k, n in enumerate(PROBE_NAMES) if mask >> k & 1]
+            st = lib().orc_solver_set_group_history(self.ptr, groups.ptr, C.c_uint32(mask & 0xFFFFFFFF), C.c_int32(_weighting(weighting)),
+                                                    C.c_uint64(interval))
+        if st == 0:
+            self._group_history = (groups, names) if groups is not None else None  # keeps the group set alive while the history reads it
+        if raise_on_error:
+            check(st)
+        return st
+
+    def record_groups(self, tag=0.0, raise_on_error=True):
+        """orc_solver_record_groups: one record of the current state with `tag` in the time slot (steady runs)"""
+        st = lib().orc_solver_record_groups(self.ptr, C.c_double(tag))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def group_history_count(self):
+        """records kept (-1 while the history is off)"""
+        return int(lib().orc_solver_group_history_count(self.ptr))
+
+    def group_history(self, first=0, count=None, full=False):
+        """the records [first, first + count) -> (times [k], values [k, G, F, 4] in the order SUM, SUM_SQ, MIN, MAX, weight [G] = W)
+        (count=None: all from first); full=True: (times, [GroupReport per record]) with the cells of the extrema as well"""
+        groups, names = getattr(self, "_group_history", None) or (None, [])
+        have = self.group_history_count()
+        if count is None:
+            count = max(have - first, 0)
+        G, F = (len(groups) if groups is not None else 0), len(names)
+        times = np.zeros(count)
+        sums, where = np.zeros((count, max(G, 1), max(F, 1), _GROUP_N)), np.zeros((count, max(G, 1), max(F, 1), 2), np.int64)
+        weight = np.zeros((max(G, 1), 2))
+        check(lib().orc_solver_group_history(self.ptr, C.c_uint64(first), C.c_uint64(count), _p(times), _p(sums), _p(weight),
+                                             where.ctypes.data_as(_I64)))
+        if full:
+            return times, [GroupReport(names, sums[k], weight, where[k]) for k in range(count)]
+        return times, sums[:, :G, :F], weight[:G, 0].copy()
+
+    def bench_group_report(self, groups, fields=("u", "v", "w", "p"), weighting="volume", reps=20):
+        """orc_bench_group_report: HIP-event (ms per group_chunk_k, ms per group_fold_k) of one launch's fields"""
+        mask, _ = _mask_of(fields, PROBE_NAMES)
+        ms = np.zeros(2)
+        check(lib().orc_bench_group_report(self.ptr, groups.ptr, C.c_uint32(mask & 0xFFFFFFFF), C.c_int32(_weighting(weighting)), C.c_int(reps), _p(ms)))
+        return float(ms[0]), float(ms[1])
 
     # ---------------------------------------------------------------- tracer particles (orc_solver_advect_tracers, ...)
     def advect(self, tracers, settings, n_substeps, record_stride=0, raise_on_error=True):
