@@ -58,8 +58,8 @@ OrcMesh *orc_mesh_create(int64_t n_cells, int64_t n_faces, int32_t n_zones,
 /* The same mesh with its cells renumbered internally by `ordering` (OrcCellOrdering; ORC_ORDER_RCM = the north star's
  * "rows sorted by RCM"): for meshes whose generator numbered the cells arbitrarily.  Callers keep speaking ORC order:
  *   ORC order       every per-cell array of orc_solver_set_fields / get_fields, orc_solve_steady / _steady_converged / _transient,
- *                   orc_solver_set_time_levels, orc_initialize_*, the scalar arm's field, source and levels, the viscosity arm's
- *                   field, orc_solver_get_viscosity / evaluate_viscosity, orc_mesh_wall_distance, orc_derived_fields /
+ *                   orc_solver_set_time_levels, orc_initialize_*, the scalar arm's field, source, levels and
+ *                   diffusivity (field and orc_solver_get_scalar_diffusivity), the viscosity arm's field, orc_solver_get_viscosity / evaluate_viscosity, orc_mesh_wall_distance, orc_derived_fields /
  *                   orc_solver_derived_fields, the fields into orc_surface_integrals / orc_boundary_fields, the time statistics
  *                   (get and set_statistics_state), the cell ids of orc_probes_get / orc_tracers_get, and everything per cell of
  *                   the volume reports (the labels and cell ids of a cell group set, the fields into orc_group_integrals, `where`)
@@ -410,6 +410,32 @@ int orc_solver_solve_scalar(OrcSolver *s, double report[4]);
 int orc_solver_last_scalar_report(OrcSolver *s, double report[4]);
 int orc_solver_assemble_scalar(OrcSolver *s, double *a, double *b);
 int orc_solver_scalar_boundary_flux(OrcSolver *s, double *per_zone);
+
+/* ---------- variable scalar diffusivity (new-build extension, orc_types.h OrcScalarDiffusivity) ----------
+ * Off by default: a solver that never calls these launches exactly what it launched before and allocates nothing new.  While a model
+ * is on, the Gamma part of the scalar system (scalar_diffusion_var_k) and the boundary term of orc_solver_scalar_boundary_flux take a
+ * per-cell Gamma evaluated on the fly; the row kernel, the solves and the flow never see it.
+ *  - orc_scalar_diffusivity_default: CONSTANT, ARITHMETIC faces, schmidt_t 0.7, beta 0, phi_ref 0, clamp 1e-12 .. 1e12.
+ *  - orc_solver_set_scalar_diffusivity(s, c): c == NULL or model CONSTANT switches the model off (the constant Gamma part comes back
+ *    bit for bit).  Refused with ORC_ERR_BAD_ARGUMENT, the solver unchanged: scalar arm off, unknown model or face mode, a non-finite
+ *    parameter, schmidt_t <= 0, a clamp that is not 0 < gamma_min <= gamma_max < inf, reserved0 != 0, FIELD without a field, EDDY unless
+ *    the viscosity arm is on with model SMAGORINSKY or FIELD.  While EDDY is on, orc_solver_set_viscosity refuses to switch that arm
+ *    off or to select a power-law or Carreau model.  orc_solver_set_scalar (NULL or new settings) switches the model off and frees
+ *    the field.
+ *  - orc_solver_set_scalar_diffusivity_field: the FIELD model's data, n_cells doubles in ORC cell order (on a partitioned mesh the
+ *    rank's array, ghost entries included), every entry positive and finite; it may be set before or while FIELD is on.
+ *  - The Gamma part is rebuilt when the model, the field, the arm's settings or a scalar condition changed; with EDDY also once at the
+ *    start of every orc_solver_solve_scalar and orc_solver_assemble_scalar (so once per time step of orc_solver_advance); with LINEAR
+ *    before every assembly from the current phi, and UD and CD1 solves then run the outer (Picard) loop as TVD solves do.
+ *  - orc_solver_get_scalar_diffusivity: Gamma per cell under the current state (the constant while the model is off), cell order as
+ *    orc_solver_get_scalar_field.
+ *  - orc_bench_scalar_diffusivity: HIP-event ms per launch of [0] scalar_diffusion_k (the constant Gamma part), [1]
+ *    scalar_diffusion_var_k of the model that is on, [2] the boundary-term pass scalar_face_var_k; all three write scratch buffers. */
+void orc_scalar_diffusivity_default(OrcScalarDiffusivity *c);
+int orc_solver_set_scalar_diffusivity(OrcSolver *s, const OrcScalarDiffusivity *c);
+int orc_solver_set_scalar_diffusivity_field(OrcSolver *s, const double *gamma /*[n_cells]*/);
+int orc_solver_get_scalar_diffusivity(OrcSolver *s, double *gamma /*[n_cells]*/);
+int orc_bench_scalar_diffusivity(OrcSolver *s, int reps, double avg_ms[3]);
 
 /* ---------- surface reports (new-build extension) ----------
  * Force, moment, mass and momentum flow, area and area-weighted pressure of every boundary zone (orc_types.h OrcSurfaceQuantity;

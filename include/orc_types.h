@@ -305,6 +305,26 @@ typedef struct OrcViscosity {
     double relaxation;          /* (0, 1]: the stored field becomes mu_old + w (mu - mu_old); 1 = none, no arithmetic */
 } OrcViscosity;
 
+/* Variable scalar diffusivity (new-build extension; orc_amd.h: orc_solver_set_scalar_diffusivity): a per-cell Gamma in the diffusion of
+ * the passive scalar.  With gamma0 = OrcScalarSettings.diffusivity, mu_c the viscosity field of the last momentum assembly
+ * (orc_solver_get_viscosity), mu_lam the solver's mu and phi_c the cell's scalar, each law is evaluated in the order written
+ * (DESIGN.md §3 "Variable scalar diffusivity"); an interior face takes OrcViscosityFace's formula on (Gamma_P, Gamma_N), a boundary
+ * VALUE face its cell's Gamma_P. */
+enum OrcScalarDiffusivityModel {
+    ORC_SCALAR_GAMMA_CONSTANT = 0, /* gamma0: the arm as it is without the model */
+    ORC_SCALAR_GAMMA_FIELD = 1,    /* the data of orc_solver_set_scalar_diffusivity_field, not clamped */
+    ORC_SCALAR_GAMMA_EDDY = 2,     /* g = gamma0 + fmax(mu_c - mu_lam, 0.) / schmidt_t, then the clamp */
+    ORC_SCALAR_GAMMA_LINEAR = 3    /* g = gamma0 * (1. + beta * (phi_c - phi_ref)), then the clamp */
+};
+typedef struct OrcScalarDiffusivity {
+    int32_t model;              /* OrcScalarDiffusivityModel */
+    int32_t face_interpolation; /* OrcViscosityFace: the same two formulas */
+    double schmidt_t;           /* EDDY: turbulent Schmidt / Prandtl number, > 0; default 0.7 */
+    double beta, phi_ref;       /* LINEAR */
+    double gamma_min, gamma_max; /* EDDY and LINEAR: Gamma = fmin(fmax(g, gamma_min), gamma_max); 0 < gamma_min <= gamma_max < inf */
+    double reserved0;           /* 0 */
+} OrcScalarDiffusivity;
+
 /* Wall damping of the Smagorinsky length (new-build extension; orc_amd.h: orc_solver_set_wall_damping): with d the wall distance of the
  * cell (orc_mesh_wall_distance, zones of type WALL) and l0 = cs * cbrt(V_P), the law's length l becomes
  *   MIN:        l = fmin(kappa * d, l0)

@@ -114,6 +114,19 @@ def lib():
             L.orc_solver_get_diffusion.restype = C.c_int
             L.orc_bench_viscosity.argtypes = [C.c_void_p, C.c_int, _f64]
             L.orc_bench_viscosity.restype = C.c_int
+        # variable scalar diffusivity (orc_amd.h "variable scalar diffusivity"): full signatures
+        if hasattr(L, "orc_solver_set_scalar_diffusivity"):
+            _f64 = C.POINTER(C.c_double)
+            L.orc_scalar_diffusivity_default.argtypes = [C.c_void_p]
+            L.orc_scalar_diffusivity_default.restype = None
+            L.orc_solver_set_scalar_diffusivity.argtypes = [C.c_void_p, C.c_void_p]
+            L.orc_solver_set_scalar_diffusivity.restype = C.c_int
+            L.orc_solver_set_scalar_diffusivity_field.argtypes = [C.c_void_p, _f64]
+            L.orc_solver_set_scalar_diffusivity_field.restype = C.c_int
+            L.orc_solver_get_scalar_diffusivity.argtypes = [C.c_void_p, _f64]
+            L.orc_solver_get_scalar_diffusivity.restype = C.c_int
+            L.orc_bench_scalar_diffusivity.argtypes = [C.c_void_p, C.c_int, _f64]
+            L.orc_bench_scalar_diffusivity.restype = C.c_int
         # wall distance and wall damping (orc_amd.h "wall distance and wall damping"): full signatures
         if hasattr(L, "orc_mesh_wall_distance"):
             _f64, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)

@@ -233,7 +233,18 @@ struct SolverState {
         DevBuf<double> snap_phi, snap_lev[2];
         int snap_levels = 0;
         bool snap_on = false;
+        // Variable diffusivity (orc_solver_set_scalar_diffusivity): off unless enabled; Gamma is a function of state that is already
+        // covered (the field as set, the viscosity arm's mu, phi), evaluated on the fly — no per-cell Gamma is kept.
+        struct Diffusivity {
+            bool on = false;
+            OrcScalarDiffusivity c{};
+            DevBuf<double> field;  // [n] the FIELD model's data as set
+            bool has_field = false;
+            bool stale = false;    // a_g / b_g were built for another model or field
+        } gd;
     } sc;
+    // the scalar's EDDY diffusivity reads vis.mu: orc_solver_set_viscosity keeps the arm on with a model that has an eddy part
+    bool scalar_gamma_reads_viscosity() const { return sc.on && sc.gd.on && sc.gd.c.model == ORC_SCALAR_GAMMA_EDDY; }
     // Variable viscosity (orc_solver_set_viscosity, viscosity.hip): off unless enabled, every buffer allocated by a set call.  While it
     // is on, a_di and b_*_di are rebuilt from `mu` ahead of every momentum assembly; off again, they are k_diffusion's.
     struct Viscosity {

@@ -10,13 +10,22 @@
 //                       rounding) and the per-face boundary term of the boundary-flux report
 //   scalar_k            one thread per row: Gamma part + UD / CD1 convection + both sides' c_f + source + time term
 // DESIGN.md "Passive scalar transport" has the discretisation and the bytes of every pass.
+// Variable diffusivity (orc_solver_set_scalar_diffusivity; DESIGN.md §3 "Variable scalar diffusivity"), opt-in: while a model is on,
+//   scalar_diffusion_var_k  replaces scalar_diffusion_k: the same loop with Gamma evaluated on the fly for the cell and for the
+//                           neighbour of every interior face (one more gather per interior face), the face value by face_viscosity
+//   scalar_face_var_k       scalar_face_k's body with the cell's Gamma in the boundary term
+//   scalar_gamma_k          Gamma per cell, for orc_solver_get_scalar_diffusivity only
+// scalar_k reads the Gamma part from a_g, b_g and never sees Gamma.
 // The system is symmetric only without convection (a flow at rest: the Gamma part alone, plus the time term on the diagonal):
 // OrcScalarSettings.solver_type = ORC_SOLVER_CG is accepted for every configuration, and CG does not test symmetry (cg.hip).
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
+#include <initializer_list>
 
 #include "assembly.hpp"
 #include "cell_order.hpp"
+#include "var_diffusion.hpp"
 
 namespace orc {
 namespace {
@@ -36,6 +45,29 @@ __device__ __forceinline__ P3 fc_of(const MeshDev &M, int f) { return p3(M.fcx[f
 bool scheme_is_tvd(int scheme) { return scheme >= ORC_MOMENTUM_TVD_LUD && scheme <= ORC_MOMENTUM_TVD_CD1; }
 
 }  // namespace
+
+// the constant Gamma of the arm without a diffusivity model
+struct GammaConst {
+    double gamma;
+    __device__ __forceinline__ double operator()(int) const { return gamma; }
+};
+
+// Gamma of cell c under a diffusivity model, THE operator order of DESIGN §3 "Variable scalar diffusivity".  x: what the law reads per
+// cell (FIELD: the field as set; EDDY: the viscosity field of the last momentum assembly; LINEAR: phi), ghost entries current.  The
+// model is the same in every lane.
+struct GammaLaw {
+    const double *x;
+    int model, harmonic;
+    double gamma0, mu_lam, schmidt_t, beta, phi_ref, gamma_min, gamma_max;
+    __device__ __forceinline__ double operator()(int c) const {
+        const double v = x[c];
+        if (model == ORC_SCALAR_GAMMA_FIELD) return v;
+        double g;
+        if (model == ORC_SCALAR_GAMMA_EDDY) g = gamma0 + fmax(v - mu_lam, 0.) / schmidt_t;
+        else g = gamma0 * (1. + beta * (v - phi_ref));  // LINEAR
+        return fmin(fmax(g, gamma_min), gamma_max);
+    }
+};
 
 // ------------------------------------------------------------------ 1. the Gamma part (once per configuration)
 // interior: D = Gamma A / |x_N - x_P| on the diagonal, -D off it; VALUE: D_b = Gamma A / |x_f - x_P| on the diagonal and
@@ -68,6 +100,48 @@ __global__ void scalar_diffusion_k(MeshDev M, SellDev P, double gamma, const int
         a_g[P.diag_pos[c]] = a_pp;
         b_g[c] = b;
     }
+}
+
+// scalar_diffusion_k's loop — the same branches, the same accumulation order of a_pp and b — with Gamma replaced by the face value of
+// (Gamma_P, Gamma_N) on interior faces and by Gamma_P on VALUE faces.  One thread per owned row, diffusion_var_k's block walk.
+__global__ __launch_bounds__(kBlock) void scalar_diffusion_var_k(MeshDev M, SellDev P, GammaLaw G, const int32_t *__restrict__ zkind,
+                                                                 const double *__restrict__ zval, double *__restrict__ a_g,
+                                                                 double *__restrict__ b_g) {
+    const int n_items = (int)M.n_own;  // cell ids are int32 (MeshDev.c0)
+    for (BlockWalk W = block_walk(n_items); W.vb < W.vb_end; W.vb += W.vb_step) {
+        const int c = W.vb * kBlock + (int)threadIdx.x;
+        if (c >= n_items) break;
+        const P3 cc = cc_of(M, c);
+        const double g_p = G(c);
+        double a_pp = 0., b = 0.;
+        for (int q = M.cfp[c]; q < M.cfp[c + 1]; ++q) {
+            const int f = M.cf[q];
+            const int c1 = M.c1[f];
+            if (c1 >= 0) {
+                const int nb = M.c0[f] == c ? c1 : M.c0[f];
+                const double d = face_viscosity(G.harmonic, g_p, G(nb)) * M.area[f] / pnorm(psub(cc_of(M, nb), cc));
+                a_g[M.cfpos[q]] = -d;
+                a_pp += d;
+            } else {
+                const int z = M.fzone[f];
+                const int k = zkind[z];
+                if (k == ORC_SCALAR_BC_VALUE) {
+                    const double d = g_p * M.area[f] / pnorm(psub(fc_of(M, f), cc));
+                    a_pp += d;
+                    b += d * zval[z];
+                } else if (k == ORC_SCALAR_BC_FLUX) {
+                    b += zval[z] * M.area[f];
+                }
+            }
+        }
+        a_g[P.diag_pos[c]] = a_pp;
+        b_g[c] = b;
+    }
+}
+
+// Gamma per cell (ghost cells included), for orc_solver_get_scalar_diffusivity only: nothing on the solve path reads it
+__global__ void scalar_gamma_k(int64_t n_cells, GammaLaw G, double *__restrict__ gamma) {
+    SC_GRID_STRIDE(c, n_cells) gamma[c] = G((int)c);
 }
 
 // ------------------------------------------------------------------ 2. Green-Gauss grad phi (TVD)
@@ -103,11 +177,12 @@ __global__ void scalar_grad_k(MeshDev M, const double *__restrict__ phi, const i
 // r = 2 (grad_U . d) / (phi_D - phi_U) - 1, phi_f = phi_U + psi(r)/2 (phi_D - phi_U), c_f = F (phi_f - phi_U) (0 when
 // phi_D == phi_U).  Boundary: the flux of phi INTO the domain through the face (VALUE: -F phi_b + D_b (phi_b - phi_P);
 // FLUX: q A - F phi_P; ZERO_GRADIENT: -F phi_P); 0 on interior faces.
-template <bool kTvd>
-__global__ __launch_bounds__(kBlock) void scalar_face_k(MeshDev M, const double *__restrict__ flux, const double *__restrict__ phi,
-                                                        const double *__restrict__ grad, const int32_t *__restrict__ zkind,
-                                                        const double *__restrict__ zval, double gamma, double rho, int scheme,
-                                                        double *__restrict__ corr, double *__restrict__ bterm) {
+// gamma_of(cell): the diffusivity a boundary VALUE face takes from its cell (GammaConst or GammaLaw).
+template <bool kTvd, class GammaOf>
+__device__ __forceinline__ void scalar_face_body(const MeshDev &M, const double *__restrict__ flux, const double *__restrict__ phi,
+                                                 const double *__restrict__ grad, const int32_t *__restrict__ zkind,
+                                                 const double *__restrict__ zval, const GammaOf &gamma_of, double rho, int scheme,
+                                                 double *__restrict__ corr, double *__restrict__ bterm) {
     const int64_t n = M.n_cells;
     SC_GRID_STRIDE(f, M.n_faces) {
         const int i = M.c0[f], j = M.c1[f];
@@ -134,7 +209,7 @@ __global__ __launch_bounds__(kBlock) void scalar_face_k(MeshDev M, const double 
             double t;
             if (k == ORC_SCALAR_BC_VALUE) {
                 const double pb = zval[z];
-                const double d = gamma * M.area[f] / pnorm(psub(fc_of(M, (int)f), cc_of(M, i)));
+                const double d = gamma_of(i) * M.area[f] / pnorm(psub(fc_of(M, (int)f), cc_of(M, i)));
                 t = -F * pb + d * (pb - pc);
             } else if (k == ORC_SCALAR_BC_FLUX) {
                 t = zval[z] * M.area[f] - F * pc;
@@ -144,6 +219,24 @@ __global__ __launch_bounds__(kBlock) void scalar_face_k(MeshDev M, const double 
             bterm[f] = t;
         }
     }
+}
+
+template <bool kTvd>
+__global__ __launch_bounds__(kBlock) void scalar_face_k(MeshDev M, const double *__restrict__ flux, const double *__restrict__ phi,
+                                                        const double *__restrict__ grad, const int32_t *__restrict__ zkind,
+                                                        const double *__restrict__ zval, double gamma, double rho, int scheme,
+                                                        double *__restrict__ corr, double *__restrict__ bterm) {
+    scalar_face_body<kTvd>(M, flux, phi, grad, zkind, zval, GammaConst{gamma}, rho, scheme, corr, bterm);
+}
+
+// the further instantiation of a diffusivity model: the boundary term with the cell's Gamma, so that the boundary-flux report and the
+// conservation identity hold with variable Gamma
+template <bool kTvd>
+__global__ __launch_bounds__(kBlock) void scalar_face_var_k(MeshDev M, const double *__restrict__ flux, const double *__restrict__ phi,
+                                                            const double *__restrict__ grad, const int32_t *__restrict__ zkind,
+                                                            const double *__restrict__ zval, GammaLaw G, double rho, int scheme,
+                                                            double *__restrict__ corr, double *__restrict__ bterm) {
+    scalar_face_body<kTvd>(M, flux, phi, grad, zkind, zval, G, rho, scheme, corr, bterm);
 }
 
 // ------------------------------------------------------------------ 4. the rows
@@ -279,20 +372,56 @@ int resolve_bcs(SolverState &s, std::vector<int32_t> &kind, std::vector<double> 
     return ORC_OK;
 }
 
-// the zone table and the Gamma part, rebuilt when the arm or a boundary condition (or a DEFAULT's zone type) changed
-int ensure_configured(SolverState &s) {
+int gamma_model(const SolverState &s) { return s.sc.gd.on ? s.sc.gd.c.model : ORC_SCALAR_GAMMA_CONSTANT; }
+
+// the law of the model that is on, reading the solver's current state
+GammaLaw gamma_law(SolverState &s) {
+    const Scalar &c = s.sc;
+    const OrcScalarDiffusivity &d = c.gd.c;
+    GammaLaw G{};
+    G.model = d.model;
+    G.x = d.model == ORC_SCALAR_GAMMA_FIELD ? c.gd.field.p : d.model == ORC_SCALAR_GAMMA_EDDY ? s.vis.mu.p : c.phi.p;
+    G.harmonic = d.face_interpolation == ORC_VISCOSITY_FACE_HARMONIC ? 1 : 0;
+    G.gamma0 = c.c.diffusivity; G.mu_lam = s.mu; G.schmidt_t = d.schmidt_t; G.beta = d.beta; G.phi_ref = d.phi_ref;
+    G.gamma_min = d.gamma_min; G.gamma_max = d.gamma_max;
+    return G;
+}
+
+// a_g and b_g of the resolved zone table: scalar_diffusion_k, or scalar_diffusion_var_k while a diffusivity model is on (LINEAR reads phi,
+// whose ghosts the caller has exchanged)
+int build_gamma_part(SolverState &s, double *a_g, double *b_g) {
+    Scalar &c = s.sc;
+    OrcMesh &m = *s.mesh;
+    if (gamma_model(s) == ORC_SCALAR_GAMMA_CONSTANT)
+        hipLaunchKernelGGL(scalar_diffusion_k, dim3(grid_for(s.n_own)), dim3(kBlock), 0, ctx().stream, m.dev(), m.pat.dev(), c.c.diffusivity,
+                           c.zkind.p, c.zval.p, a_g, b_g);
+    else
+        hipLaunchKernelGGL(scalar_diffusion_var_k, dim3(grid_for(s.n_own)), dim3(kBlock), 0, ctx().stream, m.dev(), m.pat.dev(), gamma_law(s),
+                           c.zkind.p, c.zval.p, a_g, b_g);
+    ORC_HIP(hipGetLastError());
+    return ORC_OK;
+}
+
+// The zone table and the Gamma part, rebuilt when the arm or a boundary condition (or a DEFAULT's zone type) changed, or the diffusivity
+// model or its field.  for_system (a solve or an assembly begins): EDDY rebuilds every time, from the viscosity field of the last
+// momentum assembly; LINEAR leaves the Gamma part to assemble(), which rebuilds it from the current phi every time.
+int ensure_configured(SolverState &s, bool for_system) {
     Scalar &c = s.sc;
     std::vector<int32_t> kind;
     std::vector<double> value;
     ORC_TRY(resolve_bcs(s, kind, value));
-    if (kind == c.resolved_kind && value == c.resolved_value) return ORC_OK;
-    OrcMesh &m = *s.mesh;
-    ORC_TRY(c.zkind.upload(kind.data(), kind.size()));
-    ORC_TRY(c.zval.upload(value.data(), value.size()));
-    ORC_TRY(c.a_g.zero());
-    hipLaunchKernelGGL(scalar_diffusion_k, dim3(grid_for(s.n_own)), dim3(kBlock), 0, ctx().stream, m.dev(), m.pat.dev(), c.c.diffusivity,
-                       c.zkind.p, c.zval.p, c.a_g.p, c.b_g.p);
-    ORC_HIP(hipGetLastError());
+    const bool same_table = kind == c.resolved_kind && value == c.resolved_value;
+    const int model = gamma_model(s);
+    if (same_table && !c.gd.stale && !(for_system && model == ORC_SCALAR_GAMMA_EDDY)) return ORC_OK;
+    if (!same_table) {
+        ORC_TRY(c.zkind.upload(kind.data(), kind.size()));
+        ORC_TRY(c.zval.upload(value.data(), value.size()));
+    }
+    if (model != ORC_SCALAR_GAMMA_LINEAR) {
+        ORC_TRY(c.a_g.zero());
+        ORC_TRY(build_gamma_part(s, c.a_g.p, c.b_g.p));
+        c.gd.stale = false;
+    }
     c.resolved_kind = kind;
     c.resolved_value = value;
     return ORC_OK;
@@ -307,21 +436,30 @@ int ready(SolverState &s) {
 }
 
 // the face pass (TVD: gradient and correction; always: the boundary terms) on the current phi and the arm's flux
-int face_pass(SolverState &s, bool tvd) {
+// bterm: where the boundary terms go (the arm's buffer, or the bench hook's scratch)
+int face_pass(SolverState &s, bool tvd, double *bterm) {
     Scalar &c = s.sc;
     OrcMesh &m = *s.mesh;
     HaloPlan &H = m.halo;
     const int64_t n = s.n;
+    const bool var = gamma_model(s) != ORC_SCALAR_GAMMA_CONSTANT;
     if (H.active()) ORC_TRY(H.exchange(c.phi.p));
     if (tvd) {
         hipLaunchKernelGGL(scalar_grad_k, dim3(grid_for(s.n_own)), dim3(kBlock), 0, ctx().stream, m.dev(), c.phi.p, c.zkind.p, c.zval.p, c.grad.p);
         ORC_HIP(hipGetLastError());
         if (H.active()) { double *g3[3] = {c.grad.p, c.grad.p + n, c.grad.p + 2 * n}; ORC_TRY(H.exchange(g3, 3)); }
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(scalar_face_k<true>), dim3(grid_for(m.n_faces)), dim3(kBlock), 0, ctx().stream, m.dev(), c.flux.p,
-                           c.phi.p, c.grad.p, c.zkind.p, c.zval.p, c.c.diffusivity, s.rho, c.c.scheme, c.corr.p, c.bterm.p);
+        if (var)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(scalar_face_var_k<true>), dim3(grid_for(m.n_faces)), dim3(kBlock), 0, ctx().stream, m.dev(),
+                               c.flux.p, c.phi.p, c.grad.p, c.zkind.p, c.zval.p, gamma_law(s), s.rho, c.c.scheme, c.corr.p, bterm);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(scalar_face_k<true>), dim3(grid_for(m.n_faces)), dim3(kBlock), 0, ctx().stream, m.dev(), c.flux.p,
+                               c.phi.p, c.grad.p, c.zkind.p, c.zval.p, c.c.diffusivity, s.rho, c.c.scheme, c.corr.p, bterm);
+    } else if (var) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(scalar_face_var_k<false>), dim3(grid_for(m.n_faces)), dim3(kBlock), 0, ctx().stream, m.dev(),
+                           c.flux.p, c.phi.p, c.grad.p, c.zkind.p, c.zval.p, gamma_law(s), s.rho, c.c.scheme, c.corr.p, bterm);
     } else {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(scalar_face_k<false>), dim3(grid_for(m.n_faces)), dim3(kBlock), 0, ctx().stream, m.dev(), c.flux.p,
-                           c.phi.p, c.grad.p, c.zkind.p, c.zval.p, c.c.diffusivity, s.rho, c.c.scheme, c.corr.p, c.bterm.p);
+                           c.phi.p, c.grad.p, c.zkind.p, c.zval.p, c.c.diffusivity, s.rho, c.c.scheme, c.corr.p, bterm);
     }
     ORC_HIP(hipGetLastError());
     return ORC_OK;
@@ -331,7 +469,12 @@ int assemble(SolverState &s) {
     Scalar &c = s.sc;
     OrcMesh &m = *s.mesh;
     const bool tvd = scheme_is_tvd(c.c.scheme);
-    if (tvd) ORC_TRY(face_pass(s, true));
+    if (gamma_model(s) == ORC_SCALAR_GAMMA_LINEAR) {  // Gamma(phi): the Gamma part of this round's phi
+        if (m.halo.active()) ORC_TRY(m.halo.exchange(c.phi.p));
+        ORC_TRY(c.a_g.zero());
+        ORC_TRY(build_gamma_part(s, c.a_g.p, c.b_g.p));
+    }
+    if (tvd) ORC_TRY(face_pass(s, true, c.bterm.p));
     ScalarArgs A{};
     A.flux = c.flux.p; A.corr = c.corr.p; A.a_g = c.a_g.p; A.b_g = c.b_g.p;
     A.src = c.has_source ? c.src.p : nullptr;
@@ -367,7 +510,7 @@ int stats(SolverState &s, double out[4]) {
 int solve(SolverState &s, double report[4]) {
     ORC_TRY(ready(s));
     Scalar &c = s.sc;
-    ORC_TRY(ensure_configured(s));
+    ORC_TRY(ensure_configured(s, true));
     ORC_TRY(k_scalar_face_flux(s));
     OrcSettings t = s.settings;  // the flow's guard, reduction order and GMRES restart with the scalar's solver fields
     t.solver_type = c.c.solver_type;
@@ -376,7 +519,8 @@ int solve(SolverState &s, double report[4]) {
     t.relative_convergence_threshold = c.c.relative_convergence_threshold;
     t.relaxation = c.c.relaxation;
     const bool tvd = scheme_is_tvd(c.c.scheme);
-    const uint64_t rounds = tvd ? c.c.outer_iterations : 1;
+    // the outer (Picard) loop: the TVD correction and a Gamma that depends on phi share its rounds
+    const uint64_t rounds = tvd || gamma_model(s) == ORC_SCALAR_GAMMA_LINEAR ? c.c.outer_iterations : 1;
     double rep[4] = {0., 0., 0., 0.};
     int st = ORC_OK;
     for (uint64_t k = 0; k < rounds; ++k) {
@@ -418,6 +562,20 @@ int validate(const OrcScalarSettings &c) {
     if (!std::isfinite(c.relaxation)) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: relaxation must be finite");
     if (c.outer_iterations == 0) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: outer_iterations must be at least 1");
     if (!(c.outer_tolerance >= 0.)) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: outer_tolerance must be >= 0");
+    return ORC_OK;
+}
+
+int validate(const OrcScalarDiffusivity &c) {
+    if (c.model < ORC_SCALAR_GAMMA_CONSTANT || c.model > ORC_SCALAR_GAMMA_LINEAR)
+        return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity: unknown model %d", c.model);
+    if (c.face_interpolation != ORC_VISCOSITY_FACE_ARITHMETIC && c.face_interpolation != ORC_VISCOSITY_FACE_HARMONIC)
+        return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity: unknown face interpolation %d", c.face_interpolation);
+    for (double x : {c.schmidt_t, c.beta, c.phi_ref, c.gamma_min, c.gamma_max, c.reserved0})
+        if (!std::isfinite(x)) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity: every parameter must be finite");
+    if (!(c.schmidt_t > 0.)) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity: schmidt_t must be > 0");
+    if (!(c.gamma_min > 0.) || !(c.gamma_min <= c.gamma_max))
+        return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity: the clamp needs 0 < gamma_min <= gamma_max < inf");
+    if (c.reserved0 != 0.) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity: reserved0 must be 0");
     return ORC_OK;
 }
 
@@ -553,7 +711,7 @@ int orc_solver_assemble_scalar(OrcSolver *s, double *a, double *b) {
     if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
     SolverState &st = s->st;
     ORC_TRY(ready(st));
-    ORC_TRY(ensure_configured(st));
+    ORC_TRY(ensure_configured(st, true));
     ORC_TRY(k_scalar_face_flux(st));
     ORC_TRY(assemble(st));
     OrcMesh &m = *st.mesh;
@@ -573,9 +731,9 @@ int orc_solver_scalar_boundary_flux(OrcSolver *s, double *per_zone) {
     if (!s || !per_zone) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
     SolverState &st = s->st;
     ORC_TRY(ready(st));
-    ORC_TRY(ensure_configured(st));
+    ORC_TRY(ensure_configured(st, false));
     ORC_TRY(k_scalar_face_flux(st));
-    ORC_TRY(face_pass(st, false));
+    ORC_TRY(face_pass(st, false, st.sc.bterm.p));
     OrcMesh &m = *st.mesh;
     const int Z = m.n_zones;
     if (Z > 0) {
@@ -589,6 +747,129 @@ int orc_solver_scalar_boundary_flux(OrcSolver *s, double *per_zone) {
     int h = fetch_status(st);
     if (m.halo.active()) h = comm_global_status(h);
     return h;
+}
+
+// ------------------------------------------------------------------ variable diffusivity
+static_assert(sizeof(OrcScalarDiffusivity) == 56 && offsetof(OrcScalarDiffusivity, model) == 0 &&
+                  offsetof(OrcScalarDiffusivity, face_interpolation) == 4 && offsetof(OrcScalarDiffusivity, schmidt_t) == 8 &&
+                  offsetof(OrcScalarDiffusivity, beta) == 16 && offsetof(OrcScalarDiffusivity, phi_ref) == 24 &&
+                  offsetof(OrcScalarDiffusivity, gamma_min) == 32 && offsetof(OrcScalarDiffusivity, gamma_max) == 40 &&
+                  offsetof(OrcScalarDiffusivity, reserved0) == 48,
+              "OrcScalarDiffusivity is part of the ABI (orc_amd/settings.py ScalarDiffusivity mirrors it)");
+
+void orc_scalar_diffusivity_default(OrcScalarDiffusivity *c) {
+    if (!c) return;
+    *c = OrcScalarDiffusivity{};
+    c->model = ORC_SCALAR_GAMMA_CONSTANT;
+    c->face_interpolation = ORC_VISCOSITY_FACE_ARITHMETIC;
+    c->schmidt_t = 0.7;
+    c->beta = 0.; c->phi_ref = 0.;
+    c->gamma_min = 1e-12; c->gamma_max = 1e12;
+    c->reserved0 = 0.;
+}
+
+int orc_solver_set_scalar_diffusivity(OrcSolver *s, const OrcScalarDiffusivity *c) {
+    if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
+    SolverState &st = s->st;
+    if (!st.sc.on) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: the arm is off (orc_solver_set_scalar)");
+    Scalar::Diffusivity &D = st.sc.gd;
+    if (c) ORC_TRY(validate(*c));
+    if (!c || c->model == ORC_SCALAR_GAMMA_CONSTANT) {  // back to the constant: scalar_diffusion_k's Gamma part at the next use
+        if (D.on) D.stale = true;
+        D.on = false;
+        return ORC_OK;
+    }
+    if (c->model == ORC_SCALAR_GAMMA_FIELD && !D.has_field)
+        return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity: the FIELD model needs orc_solver_set_scalar_diffusivity_field first");
+    if (c->model == ORC_SCALAR_GAMMA_EDDY &&
+        !(st.vis.on && (st.vis.c.model == ORC_VISCOSITY_SMAGORINSKY || st.vis.c.model == ORC_VISCOSITY_FIELD)))
+        return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity: EDDY needs the viscosity arm on with model SMAGORINSKY or FIELD "
+                                               "(orc_solver_set_viscosity)");
+    D.c = *c;
+    D.on = true;
+    D.stale = true;
+    return ORC_OK;
+}
+
+int orc_solver_set_scalar_diffusivity_field(OrcSolver *s, const double *gamma) {
+    if (!s || !gamma) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity field: null argument");
+    SolverState &st = s->st;
+    if (!st.sc.on) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: the arm is off (orc_solver_set_scalar)");
+    Scalar::Diffusivity &D = st.sc.gd;
+    const size_t n = (size_t)st.n;
+    for (size_t i = 0; i < n; ++i)
+        if (!(gamma[i] > 0.) || !std::isfinite(gamma[i]))
+            return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity field: entry %lld is not positive and finite", (long long)i);
+    ORC_TRY(upload_cells(*st.mesh, gamma, D.field));
+    D.has_field = true;
+    if (D.on && D.c.model == ORC_SCALAR_GAMMA_FIELD) D.stale = true;
+    return ORC_OK;
+}
+
+int orc_solver_get_scalar_diffusivity(OrcSolver *s, double *gamma) {
+    if (!s || !gamma) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar diffusivity: null argument");
+    SolverState &st = s->st;
+    if (!st.sc.on) return set_error(ORC_ERR_BAD_ARGUMENT, "scalar: the arm is off (orc_solver_set_scalar)");
+    if (gamma_model(st) == ORC_SCALAR_GAMMA_CONSTANT) {
+        std::fill(gamma, gamma + st.n, st.sc.c.diffusivity);
+        return ORC_OK;
+    }
+    OrcMesh &m = *st.mesh;
+    if (gamma_model(st) == ORC_SCALAR_GAMMA_LINEAR && m.halo.active()) ORC_TRY(m.halo.exchange(st.sc.phi.p));
+    DevBuf<double> out;
+    ORC_TRY(out.alloc((size_t)std::max<int64_t>(st.n, 1)));
+    hipLaunchKernelGGL(scalar_gamma_k, dim3(grid_for(st.n)), dim3(kBlock), 0, ctx().stream, st.n, gamma_law(st), out.p);
+    ORC_HIP(hipGetLastError());
+    return download_cells(m, out.p, gamma);
+}
+
+int orc_bench_scalar_diffusivity(OrcSolver *s, int reps, double avg_ms[3]) {
+    if (!s || !avg_ms) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
+    SolverState &st = s->st;
+    ORC_TRY(ready(st));
+    if (!st.sc.gd.on) return set_error(ORC_ERR_BAD_ARGUMENT, "bench scalar diffusivity: no model is on (orc_solver_set_scalar_diffusivity)");
+    if (reps < 1) reps = 1;
+    ORC_TRY(ensure_configured(st, false));
+    ORC_TRY(k_scalar_face_flux(st));
+    OrcMesh &m = *st.mesh;
+    Scalar &c = st.sc;
+    if (m.halo.active()) ORC_TRY(m.halo.exchange(c.phi.p));
+    DevBuf<double> a_t, b_t, bt_t;  // every pass writes here: the arm's Gamma part and boundary terms keep their bits
+    ORC_TRY(a_t.alloc((size_t)std::max<int64_t>(m.pat.padded, 1))); ORC_TRY(a_t.zero());
+    ORC_TRY(b_t.alloc((size_t)std::max<int64_t>(st.n, 1))); ORC_TRY(b_t.zero());
+    ORC_TRY(bt_t.alloc((size_t)std::max<int64_t>(m.n_faces, 1))); ORC_TRY(bt_t.zero());
+    const GammaLaw G = gamma_law(st);
+    const int g_rows = grid_for(st.n_own), g_faces = grid_for(m.n_faces);
+    hipEvent_t e0, e1;
+    ORC_HIP(hipEventCreate(&e0));
+    ORC_HIP(hipEventCreate(&e1));
+    int status = ORC_OK;
+    for (int pass = 0; pass < 3 && status == ORC_OK; ++pass) {
+        auto launch = [&] {
+            if (pass == 0)
+                hipLaunchKernelGGL(scalar_diffusion_k, dim3(g_rows), dim3(kBlock), 0, ctx().stream, m.dev(), m.pat.dev(), c.c.diffusivity,
+                                   c.zkind.p, c.zval.p, a_t.p, b_t.p);
+            else if (pass == 1)
+                hipLaunchKernelGGL(scalar_diffusion_var_k, dim3(g_rows), dim3(kBlock), 0, ctx().stream, m.dev(), m.pat.dev(), G, c.zkind.p,
+                                   c.zval.p, a_t.p, b_t.p);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(scalar_face_var_k<false>), dim3(g_faces), dim3(kBlock), 0, ctx().stream, m.dev(), c.flux.p,
+                                   c.phi.p, c.grad.p, c.zkind.p, c.zval.p, G, st.rho, c.c.scheme, c.corr.p, bt_t.p);
+            return hipGetLastError() == hipSuccess ? (int)ORC_OK : set_error(ORC_ERR_HIP, "bench scalar diffusivity: launch failed");
+        };
+        status = launch();  // warm-up
+        if (status == ORC_OK && hipEventRecord(e0, ctx().stream) != hipSuccess) status = set_error(ORC_ERR_HIP, "hipEventRecord failed");
+        for (int i = 0; i < reps && status == ORC_OK; ++i) status = launch();
+        float ms = 0.f;
+        if (status == ORC_OK && (hipEventRecord(e1, ctx().stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                                 hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+            status = set_error(ORC_ERR_HIP, "timing the scalar diffusivity passes failed");
+        avg_ms[pass] = (double)ms / reps;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    ORC_HIP(hipStreamSynchronize(ctx().stream));  // the scratch buffers are freed on return
+    return status;
 }
 
 }  // extern "C"

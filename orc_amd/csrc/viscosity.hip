@@ -21,28 +21,11 @@
 #include "assembly.hpp"
 #include "cell_order.hpp"
 #include "gradient_cell.hpp"
+#include "var_diffusion.hpp"
 
 namespace orc {
 
 namespace {
-
-// Blocks of kBlock cells; XCD g (workgroups g, g + 8, ...) walks a contiguous eighth of the blocks, so that the two cells of a face
-// mostly share one L2 (momentum_k, scalar_k, derived_cell_k).  A grid that is no multiple of 8 strides plainly.
-struct BlockWalk {
-    int vb, vb_end, vb_step;
-};
-__device__ __forceinline__ BlockWalk block_walk(int n_items) {
-    const int n_blk = (n_items + kBlock - 1) / kBlock;
-    BlockWalk w{(int)blockIdx.x, n_blk, (int)gridDim.x};
-    if ((gridDim.x & 7) == 0 && gridDim.x >= 8) {
-        const int per = (n_blk + 7) / 8;
-        const int xcd = blockIdx.x & 7;
-        w.vb = xcd * per + (int)(blockIdx.x >> 3);
-        w.vb_end = (xcd + 1) * per < n_blk ? (xcd + 1) * per : n_blk;
-        w.vb_step = gridDim.x >> 3;
-    }
-    return w;
-}
 
 struct ViscosityArgs {
     const double *u, *v, *w;
@@ -116,13 +99,6 @@ __global__ __launch_bounds__(kBlock) void viscosity_cell_k(MeshDev M, ViscosityA
         }
         A.mu[c] = mu;
     }
-}
-
-// symmetric in its two cells, and exactly mu where both hold mu: (mu + mu) * 0.5 = mu, mu / mu = 1, mu * 1 = mu
-__device__ __forceinline__ double face_viscosity(int harmonic, double mu_p, double mu_n) {
-    const double lo = fmin(mu_p, mu_n), hi = fmax(mu_p, mu_n);
-    const double mean = (lo + hi) * 0.5;
-    return harmonic ? lo * (hi / mean) : mean;
 }
 
 // diffusion_k (assembly.hip; discretization.rs:39-131) with mu replaced by the face viscosity: the same branches per zone type, the
@@ -284,6 +260,8 @@ int orc_solver_set_viscosity(OrcSolver *s, const OrcViscosity *c) {
     if (!c) {  // back to the constant mu: k_diffusion's a_di and wall terms, nothing of the arm is launched from here on
         if (st.ts.on && (st.ts.c.groups & ORC_STAT_GROUP_VISCOSITY))
             return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: the time statistics' VISCOSITY group is on (orc_solver_set_time_statistics)");
+        if (st.scalar_gamma_reads_viscosity())
+            return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: the scalar's EDDY diffusivity is on (orc_solver_set_scalar_diffusivity)");
         const bool was_on = V.on;
         ORC_HIP(hipStreamSynchronize(ctx().stream));
         const OrcWallDamping wd = V.wd;  // the damping setting is the solver's, not the arm's: it waits for the next SMAGORINSKY
@@ -293,6 +271,9 @@ int orc_solver_set_viscosity(OrcSolver *s, const OrcViscosity *c) {
         return ORC_OK;
     }
     ORC_TRY(validate(*c));
+    if (st.scalar_gamma_reads_viscosity() && c->model != ORC_VISCOSITY_SMAGORINSKY && c->model != ORC_VISCOSITY_FIELD)
+        return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: the scalar's EDDY diffusivity needs model SMAGORINSKY or FIELD "
+                                               "(orc_solver_set_scalar_diffusivity)");
     // the in-place diagonal mode is the reference's own, with the reference's constant mu (as the transient arm refuses it)
     if (st.settings.frozen_diagonals == 0) return set_error(ORC_ERR_BAD_ARGUMENT, "viscosity: not available with frozen_diagonals = 0");
     if (c->model == ORC_VISCOSITY_FIELD && !V.has_field)

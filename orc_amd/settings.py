@@ -155,6 +155,33 @@ class Viscosity(C.Structure):
         return s
 
 
+class ScalarDiffusivityModel:  # include/orc_types.h OrcScalarDiffusivityModel
+    CONSTANT, FIELD, EDDY, LINEAR = 0, 1, 2, 3
+
+
+class ScalarDiffusivity(C.Structure):
+    """OrcScalarDiffusivity: a per-cell Gamma in the scalar's diffusion (Solver.set_scalar_diffusivity) — FIELD the data of
+    Solver.set_scalar_diffusivity_field; EDDY gamma0 + max(mu_c - mu, 0) / schmidt_t on the viscosity arm's field; LINEAR
+    gamma0 (1 + beta (phi - phi_ref)); EDDY and LINEAR clamped to [gamma_min, gamma_max].  gamma0 is ScalarSettings.diffusivity."""
+    _fields_ = [
+        ("model", C.c_int32), ("face_interpolation", C.c_int32), ("schmidt_t", C.c_double), ("beta", C.c_double),
+        ("phi_ref", C.c_double), ("gamma_min", C.c_double), ("gamma_max", C.c_double), ("reserved0", C.c_double),
+    ]
+
+    @classmethod
+    def make(cls, model, face_interpolation=ViscosityFace.ARITHMETIC, **overrides):
+        """orc_scalar_diffusivity_default (schmidt_t 0.7, beta 0, phi_ref 0, clamp 1e-12 .. 1e12) with the model, the face
+        interpolation (a ViscosityFace) and any other field overridden"""
+        s = cls()
+        lib().orc_scalar_diffusivity_default(C.byref(s))
+        s.model, s.face_interpolation = int(model), int(face_interpolation)
+        for k, v in overrides.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s
+
+
 class WallDampingMode:  # include/orc_types.h OrcWallDampingMode
     NONE, MIN, VAN_DRIEST = 0, 1, 2
 

@@ -554,6 +554,36 @@ class Solver:
         check(lib().orc_solver_scalar_boundary_flux(self.ptr, _p(out)))
         return out
 
+    # ---------------------------------------------------------------- variable scalar diffusivity (orc_solver_set_scalar_diffusivity)
+    def set_scalar_diffusivity(self, cfg=None, raise_on_error=True):
+        """a settings.ScalarDiffusivity puts a per-cell Gamma into the scalar's diffusion (FIELD, EDDY on the viscosity arm's field,
+        LINEAR in phi); None or model CONSTANT switches it off and puts the constant Gamma part back.  Needs set_scalar()."""
+        st = lib().orc_solver_set_scalar_diffusivity(self.ptr, C.byref(cfg) if cfg is not None else None)
+        if raise_on_error:
+            check(st)
+        return st
+
+    def set_scalar_diffusivity_field(self, gamma, raise_on_error=True):
+        """the FIELD model's data: one Gamma per cell (> 0, finite), cell order as set_scalar_field()"""
+        gamma = _f64(gamma)
+        st = lib().orc_solver_set_scalar_diffusivity_field(self.ptr, _p(gamma))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def scalar_diffusivity(self):
+        """Gamma per cell under the current state (the constant while no model is on), cell order as get_scalar_field()"""
+        g = np.empty(self.n)
+        check(lib().orc_solver_get_scalar_diffusivity(self.ptr, _p(g)))
+        return g
+
+    def bench_scalar_diffusivity(self, reps=50):
+        """orc_bench_scalar_diffusivity: ms per launch of (scalar_diffusion_k, scalar_diffusion_var_k of the model that is on, the
+        boundary-term pass scalar_face_var_k); needs set_scalar_diffusivity()"""
+        ms = np.zeros(3)
+        check(lib().orc_bench_scalar_diffusivity(self.ptr, C.c_int(reps), _p(ms)))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
     # ---------------------------------------------------------------- variable viscosity (orc_solver_set_viscosity)
     def set_viscosity(self, v=None, raise_on_error=True):
         """a settings.Viscosity turns the per-cell viscosity on (evaluated on the current fields and a_di rebuilt at once, then ahead
