@@ -367,7 +367,8 @@ int orc_solver_assemble_pressure(OrcSolver *s, double *a_p, double *b_p);
  *    inner_iterations SIMPLE iterations, fewer once both correction norms (report slots 6, 7) are below inner_tolerance times
  *    their values at the first inner iteration.  report (may be NULL): 10 doubles per step, the 8 of orc_solver_iterate for
  *    the last inner iteration, the inner iterations used, and the time reached since the arm was enabled.
- *  - orc_solver_snapshot / orc_solver_restore include the time levels, their count and the time while the arm is on. */
+ *  - orc_solver_snapshot / orc_solver_restore include the time levels, their count and the time while the arm is on.
+ *  - the step is OrcTransient.dt throughout unless an entry of "adaptive time stepping" below changes it. */
 int orc_solver_set_transient(OrcSolver *s, const OrcTransient *t);
 int orc_solver_set_time_levels(OrcSolver *s, const double *u_n, const double *v_n, const double *w_n, const double *u_nm1,
                                const double *v_nm1, const double *w_nm1);
@@ -376,6 +377,46 @@ int orc_solver_advance(OrcSolver *s, uint64_t time_steps, double *report);
  * steps with the last inner iteration's report (iteration = time step, ms_per_iter = ms per time step) */
 int orc_solve_transient(OrcMesh *m, double *u, double *v, double *w, double *p, const OrcSettings *settings, double rho, double mu,
                         const OrcTransient *t, uint64_t time_steps, uint64_t reporting_interval, OrcReportFn report_cb, void *user);
+
+/* ---------- adaptive time stepping (new-build extension, orc_types.h OrcTimeStepControl) ----------
+ * Off by default: a solver that calls none of these entries launches what it launched before and produces the same bits.
+ * The time state of the arm: `time` reached, dt_next (the step orc_solver_advance takes next; OrcTransient.dt at first), dt_last (the
+ * step that led from level n-1 to level n) and dt_before_last.  The time terms of the momentum systems and of the scalar read
+ * w = dt_next / dt_last (OrcTimeStepControl above); the statistics weight, the tracer substep, the scalar time term, the time reached
+ * and the history tags follow the step actually taken.
+ *  - orc_solver_courant: rate_max = the largest ORC_DERIVED_CONVECTIVE_RATE of the solver's current u, v, w over the owned cells (its
+ *    bits), *cell = the smallest ORC id among the cells that attain it, rate (may be NULL) = the per-cell values in ORC order, from the
+ *    same launch.  A NaN rate anywhere makes rate_max NaN.  On a partitioned mesh rate_max is the maximum over all ranks (the same
+ *    bits on every rank) and *cell is -1.  Reads the fields, writes none; two calls on one state give the same bits.
+ *  - orc_time_step_next: the law of OrcTimeStepControl on the host, no device needed.  An invalid control, a dt that is not positive
+ *    and finite, or a NaN, negative or infinite rate_max is ORC_ERR_BAD_ARGUMENT with *dt_next untouched.
+ *  - orc_solver_set_time_step: dt_next; levels, time and history are kept.  From now on every step appends a history row.
+ *  - orc_solver_set_time_step_control: c == NULL turns control off.  Otherwise, after every interval-th step from now on,
+ *    orc_solver_advance reduces the rate on the fields just reached (one more synchronisation), and sets dt_next by the law; a NaN or
+ *    infinite rate there is ORC_ERR_SOLUTION_DIVERGED.  Refused: a control whose [dt_min, dt_max] does not contain dt_next.
+ *    The choice lags one step: no step is rejected and repeated.
+ *  - orc_solver_get_time_state (any output may be NULL) / orc_solver_set_time_state: with orc_solver_set_time_levels and
+ *    orc_solver_set_time_step a run continues bit for bit.  orc_solver_set_time_levels alone assumes dt_last = dt_before_last = dt_next.
+ *  - orc_solver_time_step_count / _history: one row per step while control is on or a manual step has been set — time reached, dt
+ *    used, rate_max at its end (NaN where it was not measured), cell (-1 likewise and on a partitioned mesh).  A range past the
+ *    history is ORC_ERR_BAD_ARGUMENT.
+ *  - orc_solver_set_transient resets the time state, turns control off and clears the history; orc_solver_snapshot / _restore carry
+ *    the time state (time, dt_next, dt_last, dt_before_last and the controller's step count), not the history.
+ *  - orc_bench_courant: HIP-event average ms over `reps` of the reduction (courant_k and its fold) on the solver's current fields;
+ *    orc_bench_derived_rate: the same for derived_cell_k selecting ORC_DERIVED_CONVECTIVE_RATE alone.
+ * Refused with ORC_ERR_BAD_ARGUMENT, nothing changed: a null solver, the three set entries without the transient arm, a value that
+ * is not positive and finite (time >= 0), a control outside the ranges of OrcTimeStepControl. */
+void orc_time_step_control_default(OrcTimeStepControl *c);
+int orc_time_step_next(const OrcTimeStepControl *c, double dt, double rate_max, double *dt_next);
+int orc_solver_courant(OrcSolver *s, double *rate_max, int64_t *cell, double *rate);
+int orc_solver_set_time_step(OrcSolver *s, double dt);
+int orc_solver_set_time_step_control(OrcSolver *s, const OrcTimeStepControl *c);
+int orc_solver_get_time_state(OrcSolver *s, double *time, double *dt_next, double *dt_last, double *dt_before_last);
+int orc_solver_set_time_state(OrcSolver *s, double time, double dt_last, double dt_before_last);
+int64_t orc_solver_time_step_count(OrcSolver *s);
+int orc_solver_time_step_history(OrcSolver *s, uint64_t first, uint64_t count, double *out);
+int orc_bench_courant(OrcSolver *s, int reps, double *avg_ms);
+int orc_bench_derived_rate(OrcSolver *s, int reps, double *avg_ms);
 
 /* ---------- passive scalar transport (new-build extension, orc_types.h OrcScalarSettings) ----------
  * Off by default: a solver that never calls orc_solver_set_scalar runs exactly the code it ran before.  The scalar is carried

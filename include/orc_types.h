@@ -155,7 +155,8 @@ typedef struct OrcSettings {
 } OrcSettings;
 
 /* Implicit time stepping (new-build extension; ORC's roadmap lists "Iterate transient" as not done).  With c = rho V_P / dt
- * the three momentum systems get  Euler: diag += c, b += c u_n;  BDF2: diag += 1.5 c, b += c (2 u_n - 0.5 u_nm1).
+ * the three momentum systems get  Euler: diag += c, b += c u_n;  BDF2: diag += 1.5 c, b += c (2 u_n - 0.5 u_nm1)
+ * (the fixed-step values of the coefficients under OrcTimeStepControl below).
  * orc_amd.h: orc_solver_set_transient, orc_solver_advance, orc_solve_transient. */
 enum OrcTimeScheme { ORC_TIME_EULER = 0, ORC_TIME_BDF2 = 1 };
 
@@ -166,6 +167,23 @@ typedef struct OrcTransient {
     uint64_t inner_iterations; /* >= 1: SIMPLE iterations per time step at most */
     double inner_tolerance;    /* >= 0; 0 = always inner_iterations */
 } OrcTransient;
+
+/* Adaptive time stepping (new-build extension): the rule by which orc_solver_advance chooses the next step from the largest
+ * convective rate max_c sum_f |U_f . n| A / (2 V_c) of the fields just reached (orc_solver_courant).  The law, in this operator order:
+ *     want = rate_max > 0 ? target_courant / rate_max : dt_max
+ *     next = min(max(want, dt * max_shrink), dt * max_growth)
+ *     next = min(max(next, dt_min), dt_max)
+ * With a changing step, w = dt / dt_last, BDF2 reads  diag += a0 c, b += c (a1 u_n - a2 u_nm1),  a0 = (1 + 2 w) / (1 + w),
+ * a1 = 1 + w, a2 = (w w) / (1 + w); w = 1 gives 1.5, 2 and 0.5 exactly.
+ * orc_amd.h: orc_solver_set_time_step_control, orc_time_step_next and their companions. */
+typedef struct OrcTimeStepControl {
+    double target_courant;        /* > 0, finite */
+    double dt_min, dt_max;        /* 0 < dt_min <= dt_max, finite */
+    double max_growth;            /* in [1, 2]: dt_next <= max_growth * dt (BDF2's zero-stability needs a ratio below 1 + sqrt 2) */
+    double max_shrink;            /* in (0, 1]: dt_next >= max_shrink * dt */
+    uint64_t interval;            /* >= 1: dt is chosen anew after every interval-th step */
+    int32_t reserved0, reserved1; /* 0 */
+} OrcTimeStepControl;
 
 /* Passive scalar transport (new-build extension; ORC has no scalar equation):
  *     rho dphi/dt + div(rho U phi) = div(Gamma grad phi) + S

@@ -244,6 +244,31 @@ def lib():
             L.orc_solver_group_history.restype = C.c_int
             L.orc_bench_group_report.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int, _f64]
             L.orc_bench_group_report.restype = C.c_int
+        # adaptive time stepping (orc_amd.h "adaptive time stepping"): full signatures
+        if hasattr(L, "orc_solver_courant"):
+            _f64, _i64 = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+            L.orc_time_step_control_default.argtypes = [C.c_void_p]
+            L.orc_time_step_control_default.restype = None
+            L.orc_time_step_next.argtypes = [C.c_void_p, C.c_double, C.c_double, _f64]
+            L.orc_time_step_next.restype = C.c_int
+            L.orc_solver_courant.argtypes = [C.c_void_p, _f64, _i64, _f64]
+            L.orc_solver_courant.restype = C.c_int
+            L.orc_solver_set_time_step.argtypes = [C.c_void_p, C.c_double]
+            L.orc_solver_set_time_step.restype = C.c_int
+            L.orc_solver_set_time_step_control.argtypes = [C.c_void_p, C.c_void_p]
+            L.orc_solver_set_time_step_control.restype = C.c_int
+            L.orc_solver_get_time_state.argtypes = [C.c_void_p, _f64, _f64, _f64, _f64]
+            L.orc_solver_get_time_state.restype = C.c_int
+            L.orc_solver_set_time_state.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
+            L.orc_solver_set_time_state.restype = C.c_int
+            L.orc_solver_time_step_count.argtypes = [C.c_void_p]
+            L.orc_solver_time_step_count.restype = C.c_int64
+            L.orc_solver_time_step_history.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, _f64]
+            L.orc_solver_time_step_history.restype = C.c_int
+            L.orc_bench_courant.argtypes = [C.c_void_p, C.c_int, _f64]
+            L.orc_bench_courant.restype = C.c_int
+            L.orc_bench_derived_rate.argtypes = [C.c_void_p, C.c_int, _f64]
+            L.orc_bench_derived_rate.restype = C.c_int
         # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
         if hasattr(L, "orc_debug_amg_setup_stats"):
             L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]

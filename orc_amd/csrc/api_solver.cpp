@@ -31,6 +31,10 @@ int snapshot_walk(SolverState &t, bool save) {
         for (int k = 0; k < 6; ++k) ORC_TRY(copy(t.lev[k], t.snap_lev[k], n));
         keep(t.time_levels, t.snap_time_levels);
         keep(t.time, t.snap_time);
+        keep(t.dt, t.snap_dt);  // the time state of adaptive stepping; the step history is left alone
+        keep(t.dt_last, t.snap_dt_last);
+        keep(t.dt_before_last, t.snap_dt_before_last);
+        keep(t.ctl.step, t.ctl.snap_step);
     }
     if (arm(t.sc.on, t.sc.snap_on)) {  // the scalar, its levels and their count (orc_solver_set_scalar)
         ORC_TRY(copy(t.sc.phi, t.sc.snap_phi, n1));

@@ -388,14 +388,16 @@ __global__ __launch_bounds__(kBlock) void peclet_stats_k(const double *__restric
 
 // ------------------------------------------------------------------ implicit time term (transient arm)
 // After momentum_k, per owned cell with c = rho V_P / dt:  Euler  diag += c,     b += c u_n;
-//                                                          BDF2   diag += 1.5 c, b += c (2 u_n - 0.5 u_nm1).
+//                                                          BDF2   diag += a0 c,  b += c (a1 u_n - a2 u_nm1),
+// a0, a1, a2 the variable-step coefficients of w = dt / dt_last, formed once on the host (SolverState::time_coef): 1.5, 2, 0.5 exactly
+// for a fixed step, and a product with 2 or 0.5 is exact, so a fixed-step run keeps the bits the literals gave.
 // The new diagonal also goes to du/dv/dw (written, never read), so Rhie-Chow and the p' coefficients see the time term.
 // One pass over the three systems; the diagonal slots sit at depth k of their 64-row slice (SellDev::diag_pos), so a wave's
 // read-modify-writes fall into as many 512-byte segments as its rows have distinct diagonal depths.
 struct TimeTermArgs {
     const double *un, *vn, *wn, *unm1, *vnm1, *wnm1;
     double *a_u, *a_v, *a_w, *b_u, *b_v, *b_w, *du, *dv, *dw;
-    double rho, dt;
+    double rho, dt, a0, a1, a2;
 };
 
 template <bool kBdf2>
@@ -406,10 +408,10 @@ __global__ __launch_bounds__(kBlock) void time_term_k(int64_t n_own, const doubl
         const int dpos = diag_pos[c];
         double add, su, sv, sw;
         if (kBdf2) {
-            add = 1.5 * coef;
-            su = coef * (2.0 * T.un[c] - 0.5 * T.unm1[c]);
-            sv = coef * (2.0 * T.vn[c] - 0.5 * T.vnm1[c]);
-            sw = coef * (2.0 * T.wn[c] - 0.5 * T.wnm1[c]);
+            add = T.a0 * coef;
+            su = coef * (T.a1 * T.un[c] - T.a2 * T.unm1[c]);
+            sv = coef * (T.a1 * T.vn[c] - T.a2 * T.vnm1[c]);
+            sw = coef * (T.a1 * T.wn[c] - T.a2 * T.wnm1[c]);
         } else {
             add = coef;
             su = coef * T.un[c];
@@ -621,8 +623,9 @@ int k_momentum(SolverState &s, double *peclet_host) {
 int k_time_term(SolverState &s) {
     OrcMesh &m = *s.mesh;
     const bool bdf2 = s.tr.scheme == ORC_TIME_BDF2 && s.time_levels >= 2;  // BDF2 starts as Euler while one level is known
+    const SolverState::TimeCoef k = s.time_coef();
     TimeTermArgs T{s.lev[0].p, s.lev[1].p, s.lev[2].p, s.lev[3].p, s.lev[4].p, s.lev[5].p, s.a_u.p, s.a_v.p, s.a_w.p,
-                   s.b_u.p, s.b_v.p, s.b_w.p, s.du.p, s.dv.p, s.dw.p, s.rho, s.tr.dt};
+                   s.b_u.p, s.b_v.p, s.b_w.p, s.du.p, s.dv.p, s.dw.p, s.rho, s.dt, k.a0, k.a1, k.a2};
     const int g = grid_for(s.n_own);
     if (bdf2)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(time_term_k<true>), dim3(g), dim3(kBlock), 0, ctx().stream, s.n_own, m.vol.p, m.pat.diag_pos.p, T);

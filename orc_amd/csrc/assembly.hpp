@@ -196,6 +196,33 @@ struct SolverState {
     int snap_time_levels = 0;
     double snap_time = 0.;
     bool snap_transient = false;
+    // Adaptive time stepping (orc_solver_set_time_step / _control, api_transient.cpp): dt is the step the next orc_solver_advance step
+    // takes (OrcTransient.dt until someone changes it), dt_last the one that led from level n-1 to n.  Every arm reads dt, never the
+    // OrcTransient; with nothing changed dt_last == dt and time_coef() is 1.5 / 2 / 0.5 exactly.
+    double dt = 0., dt_last = 0., dt_before_last = 0.;
+    double snap_dt = 0., snap_dt_last = 0., snap_dt_before_last = 0.;
+    struct TimeCoef { double a0, a1, a2; };
+    TimeCoef time_coef() const {  // variable-step BDF2 on the host, once per launch: w = dt / dt_last
+        const double w = dt / dt_last;
+        return {(1. + 2. * w) / (1. + w), 1. + w, (w * w) / (1. + w)};
+    }
+    struct StepControl {
+        bool on = false;           // orc_solver_set_time_step_control
+        bool manual = false;       // orc_solver_set_time_step was called: rows are recorded without control too
+        OrcTimeStepControl c{};
+        uint64_t step = 0, snap_step = 0;  // steps since control was set
+        std::vector<double> history;       // 4 doubles per recorded step
+    } ctl;
+    // The Courant reduction (courant.hip): off until orc_solver_courant or a controlled step asks; every buffer its own.
+    struct Courant {
+        DevBuf<double> part_v, out;   // [kMaxPartials] workgroup maxima; [4] rate_max, id, (rate_max or +inf, NaN flag) for the all-reduce
+        DevBuf<int64_t> part_id;      // [kMaxPartials] their ORC ids
+        DevBuf<int32_t> orc_id;       // ORC id of every internal cell; empty when the numbering is ORC's own
+        DevBuf<int> status;
+        double *raw = nullptr;        // [2] pinned: where the pair lands
+        bool ready = false;
+        ~Courant() { if (raw) (void)hipHostFree(raw); }
+    } cr;
     bool diagonals_assembled = false;  // k_momentum has written du/dv/dw at least once (Rhie-Chow face fluxes need them)
     // Residual monitors (orc_solver_set_monitors, residuals.hip): off unless enabled.  The partial sums and the folded raw slots are
     // the monitor's own — s.partials / s.scal belong to the Peclet statistics and the correction.  dev: the folded slots in
@@ -335,14 +362,13 @@ struct SolverState {
         }
     } gh;
     // Tracer tracking (orc_solver_set_tracer_tracking, tracers.hip): off unless enabled.  Every step of orc_solver_advance moves the set
-    // by `substeps` substeps of h in the new velocity; the kernel's status word is copied to the pinned `raw` behind it and looked at
+    // by `substeps` substeps of dt / substeps (the step just taken) in the new velocity; the kernel's status word is copied to the pinned `raw` behind it and looked at
     // by the next step.  Reads the fields, never writes them; snapshot / restore leave the set alone.
     struct TracerTracking {
         bool on = false;
         OrcTracers *set = nullptr;
         OrcTracerSettings c{};
         uint32_t substeps = 0;
-        double h = 0.;                    // dt / substeps, computed once on the host
         DevBuf<int> status;
         int *raw = nullptr;               // pinned
         hipEvent_t copied = nullptr;
@@ -356,7 +382,7 @@ struct SolverState {
             if (raw) (void)hipHostFree(raw);
             copied = nullptr; raw = nullptr;
             status.release();
-            on = false; pending = false; set = nullptr; substeps = 0; h = 0.;
+            on = false; pending = false; set = nullptr; substeps = 0;
         }
     } tt;
 };
@@ -464,6 +490,10 @@ int tracers_step_dev(SolverState &s);
 // group history (groups.hip): what orc_solver_advance runs last — counts the step and, when the history is on and the step is due,
 // reduces one record on the device and starts its copy to the host; asynchronous on ctx().stream, nothing while it is off
 int groups_step_dev(SolverState &s);
+// the Courant reduction (courant.hip): the largest convective rate of the current u, v, w over the owned cells (all ranks' on a
+// partitioned mesh) and the smallest ORC id that attains it (-1 on a partitioned mesh) to the host; rate_dev (may be null): the per-cell
+// values, internal order, n long, from the same launch.  Exchanges the fields' ghosts first; returns with the stream synchronised.
+int courant_dev(SolverState &s, double *rate_max, int64_t *cell, double *rate_dev);
 
 }  // namespace orc
 

@@ -230,6 +230,42 @@ int orc_derived_fields(OrcMesh *m, const double *u, const double *v, const doubl
     return derived_fields_dev(*m, dev[0].p, dev[1].p, dev[2].p, *settings, mask, out);
 }
 
+// the comparison partner of orc_bench_courant: derived_cell_k selecting the convective rate alone (it forms the gradient as well and
+// stores n doubles), HIP-event average ms over `reps` on the solver's current fields
+int orc_bench_derived_rate(OrcSolver *s, int reps, double *avg_ms) {
+    ORC_TRY(ensure_init());
+    if (!s || !avg_ms) return set_error(ORC_ERR_BAD_ARGUMENT, "bench derived rate: null argument");
+    SolverState &st = s->st;
+    OrcMesh &m = *st.mesh;
+    if (reps < 1) reps = 1;
+    DevBuf<double> dev;
+    DevBuf<int> status;
+    ORC_TRY(dev.alloc((size_t)std::max<int64_t>(m.n_cells, 1)));
+    ORC_TRY(status.alloc(1));
+    ORC_TRY(status.zero());
+    DerivedArgs A{st.u.p, st.v.p, st.w.p, dev.p, 1u << ORC_DERIVED_CONVECTIVE_RATE};
+    const int grid = grid_for(m.n_own);
+    const bool lsq = st.settings.gradient_reconstruction == ORC_GRAD_LEAST_SQUARES;
+    auto launch = [&]() {
+        if (lsq) hipLaunchKernelGGL(HIP_KERNEL_NAME(derived_cell_k<true>), dim3(grid), dim3(kBlock), 0, ctx().stream, m.dev(), A, status.p);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(derived_cell_k<false>), dim3(grid), dim3(kBlock), 0, ctx().stream, m.dev(), A, status.p);
+    };
+    hipEvent_t e0, e1;
+    ORC_HIP(hipEventCreate(&e0));
+    ORC_HIP(hipEventCreate(&e1));
+    launch();  // warm-up
+    bool ok = hipEventRecord(e0, ctx().stream) == hipSuccess;
+    for (int i = 0; i < reps; ++i) launch();
+    float ms = 0.f;
+    ok = ok && hipEventRecord(e1, ctx().stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    ORC_HIP(hipStreamSynchronize(ctx().stream));  // dev is freed on return
+    if (!ok || hipGetLastError() != hipSuccess) return set_error(ORC_ERR_HIP, "timing derived_cell_k failed");
+    *avg_ms = (double)ms / reps;
+    return ORC_OK;
+}
+
 int orc_solver_boundary_fields(OrcSolver *s, uint32_t mask, double *out) {
     ORC_TRY(ensure_init());
     if (!s || !out) return set_error(ORC_ERR_BAD_ARGUMENT, "boundary fields: null argument");

@@ -1,5 +1,5 @@
 // gradient_cell.hpp — the per-cell gradient arithmetic of the assembly (K9), shared by grad_u_k / grad_u_lsq_k / grad_p_k / grad_p_lsq_k
-// (assembly.hip), derived_cell_k (derived.hip), viscosity_cell_k (viscosity.hip) and probe_sample_k (probes.hip): the small vector type,
+// (assembly.hip), derived_cell_k (derived.hip), courant_k (courant.hip), viscosity_cell_k (viscosity.hip) and probe_sample_k (probes.hip): the small vector type,
 // the boundary-value rules, the two per-cell bodies of the velocity gradient and the two of the pressure gradient, the strain-rate
 // magnitude; the grid-stride loop of the assembly kernels (assembly.hip, initialize.hip).
 // Device code only.  Every operation and its order are the reference's; a kernel that calls a body gets the same bits as any other.
@@ -105,10 +105,15 @@ __device__ __forceinline__ void inv_times3(const double ainv[3][3], const double
     }
 }
 
+// |U_f . n| A of one face, U_f . n = (n.x U.x + n.y U.y) + n.z U.z: the term of the convective rate.  The same bits for n and -n, and
+// for the U_f of face_velocity_linear however its two cells are ordered, so every face loop below adds the same number.
+__device__ __forceinline__ double conv_face_term(V3 nrm, V3 fv, double area) { return fabs((nrm.x * fv.x + nrm.y * fv.y) + nrm.z * fv.z) * area; }
+
 // The Green-Gauss velocity gradient of cell c (solver.rs:784-801): rows tx, ty, tz = grad u, grad v, grad w, the cell's faces in
-// Cell.face_indices order.  kConv: also conv = sum over the same faces of |U_f . n| A with U_f . n = (n.x U.x + n.y U.y) + n.z U.z
-// (the convective rate of derived.hip; a face in a refused zone takes no part in either).
-template <bool kConv>
+// Cell.face_indices order.  kConv: also conv = sum over the same faces of |U_f . n| A (the convective rate of derived.hip; a face in a
+// refused zone takes no part in either).  kGrad = false: the face loop with the gradient rows left out (they come back 0) — what
+// courant_k (courant.hip) runs; conv has the bits of either reconstruction's, since both add conv_face_term of the same faces in order.
+template <bool kConv, bool kGrad = true>
 __device__ __forceinline__ void grad_u_gg_cell(const MeshDev &M, const double *__restrict__ u, const double *__restrict__ v,
                                                const double *__restrict__ w, int64_t c, int *status, V3 &tx, V3 &ty, V3 &tz, double &conv) {
     const double vol = M.vol[c];
@@ -122,11 +127,13 @@ __device__ __forceinline__ void grad_u_gg_cell(const MeshDev &M, const double *_
         const V3 fv = face_velocity_linear(M, u, v, w, f, zt, z);
         V3 nrm = face_normal(M, f);
         if (M.c0[f] != c) nrm = vneg(nrm);
-        const V3 nn = vmuls(nrm, M.area[f] / vol);  // :799
-        tx = vadd(tx, mk(fv.x * nn.x, fv.x * nn.y, fv.x * nn.z));  // outer (lib.rs:275-293)
-        ty = vadd(ty, mk(fv.y * nn.x, fv.y * nn.y, fv.y * nn.z));
-        tz = vadd(tz, mk(fv.z * nn.x, fv.z * nn.y, fv.z * nn.z));
-        if (kConv) conv = conv + fabs((nrm.x * fv.x + nrm.y * fv.y) + nrm.z * fv.z) * M.area[f];
+        if (kGrad) {
+            const V3 nn = vmuls(nrm, M.area[f] / vol);  // :799
+            tx = vadd(tx, mk(fv.x * nn.x, fv.x * nn.y, fv.x * nn.z));  // outer (lib.rs:275-293)
+            ty = vadd(ty, mk(fv.y * nn.x, fv.y * nn.y, fv.y * nn.z));
+            tz = vadd(tz, mk(fv.z * nn.x, fv.z * nn.y, fv.z * nn.z));
+        }
+        if (kConv) conv = conv + conv_face_term(nrm, fv, M.area[f]);
     }
 }
 
@@ -161,8 +168,7 @@ __device__ __forceinline__ void grad_u_lsq_cell(const MeshDev &M, const double *
         const double x[3] = {d.x, d.y, d.z};
         L.add_row(x, b, 3);
         if (kConv) {
-            const V3 nrm = face_normal(M, f);  // |U_f . n| is the same for n and -n
-            conv = conv + fabs((nrm.x * lin.x + nrm.y * lin.y) + nrm.z * lin.z) * M.area[f];
+            conv = conv + conv_face_term(face_normal(M, f), lin, M.area[f]);  // |U_f . n| is the same for n and -n
         }
     }
 #pragma unroll

@@ -245,7 +245,7 @@ struct ScalarArgs {
     const int32_t *zkind;
     const double *zval;
     double *a, *b;
-    double rho, dt;
+    double rho, dt, a0, a1, a2;
     int cd1, tvd, time;  // time: 0 none, 1 Euler, 2 BDF2
 };
 
@@ -292,8 +292,8 @@ __global__ __launch_bounds__(kBlock) void scalar_k(MeshDev M, SellDev P, ScalarA
         if (A.time) {
             const double coef = (A.rho * M.vol[c]) / A.dt;
             if (A.time == 2) {
-                a_pp += 1.5 * coef;
-                b += coef * (2.0 * A.phi_n[c] - 0.5 * A.phi_nm1[c]);
+                a_pp += A.a0 * coef;  // the variable-step coefficients of time_term_k: 1.5, 2, 0.5 exactly for a fixed step
+                b += coef * (A.a1 * A.phi_n[c] - A.a2 * A.phi_nm1[c]);
             } else {
                 a_pp += coef;
                 b += coef * A.phi_n[c];
@@ -481,7 +481,8 @@ int assemble(SolverState &s) {
     A.phi_n = c.lev[0].p; A.phi_nm1 = c.lev[1].p;
     A.zkind = c.zkind.p; A.zval = c.zval.p;
     A.a = c.a.p; A.b = c.b.p;
-    A.rho = s.rho; A.dt = s.tr.dt;
+    A.rho = s.rho; A.dt = s.dt;
+    { const SolverState::TimeCoef k = s.time_coef(); A.a0 = k.a0; A.a1 = k.a1; A.a2 = k.a2; }
     A.cd1 = c.c.scheme == ORC_MOMENTUM_CD1;
     A.tvd = tvd;
     A.time = (s.transient && c.levels > 0) ? ((s.tr.scheme == ORC_TIME_BDF2 && c.levels >= 2) ? 2 : 1) : 0;

@@ -177,7 +177,7 @@ int stats_step_dev(SolverState &s) {
     if (!T.on) return ORC_OK;
     ++T.step;
     if (T.step < T.c.start_step || (T.step - T.c.start_step) % T.c.interval != 0) return ORC_OK;
-    return sample(s, s.tr.dt);
+    return sample(s, s.dt);
 }
 
 }  // namespace orc

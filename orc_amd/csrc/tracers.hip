@@ -214,7 +214,7 @@ int tracers_step_dev(SolverState &s) {
     if (!T.on) return ORC_OK;
     ORC_TRY(tracking_flush(s));  // the previous step's word: this step's iterations have synchronised the stream since
     OrcTracers &t = *T.set;
-    ORC_TRY(launch_advect(s, T.c, T.h, view(t.st[t.cur]), view(t.st[1 - t.cur]), t.n, T.substeps, nullptr, nullptr, T.status.p));
+    ORC_TRY(launch_advect(s, T.c, s.dt / (double)T.substeps, view(t.st[t.cur]), view(t.st[1 - t.cur]), t.n, T.substeps, nullptr, nullptr, T.status.p));
     t.cur = 1 - t.cur;  // every reader of the set is ordered behind the launch on the stream
     ORC_HIP(hipMemcpyAsync(T.raw, T.status.p, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
     ORC_HIP(hipEventRecord(T.copied, ctx().stream));
@@ -426,7 +426,6 @@ int orc_solver_set_tracer_tracking(OrcSolver *s, OrcTracers *t, const OrcTracerS
     T.set = t;
     T.c = *c;
     T.substeps = substeps_per_step;
-    T.h = st.tr.dt / (double)substeps_per_step;
     T.on = true;
     return ORC_OK;
 }

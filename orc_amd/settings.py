@@ -88,7 +88,7 @@ class TimeScheme:  # include/orc_types.h OrcTimeScheme
 
 
 class Transient(C.Structure):
-    """OrcTransient: implicit time stepping with a fixed step (Solver.set_transient, solve_transient)."""
+    """OrcTransient: implicit time stepping (Solver.set_transient, solve_transient); dt is the step, the first one under a TimeStepControl."""
     _fields_ = [
         ("dt", C.c_double), ("scheme", C.c_int32), ("reserved0", C.c_int32),
         ("inner_iterations", C.c_uint64), ("inner_tolerance", C.c_double),
@@ -97,6 +97,31 @@ class Transient(C.Structure):
     @classmethod
     def make(cls, dt, scheme=TimeScheme.Euler, inner_iterations=20, inner_tolerance=0.0):
         return cls(dt=dt, scheme=scheme, reserved0=0, inner_iterations=inner_iterations, inner_tolerance=inner_tolerance)
+
+
+class TimeStepControl(C.Structure):
+    """OrcTimeStepControl: the rule by which Solver.advance chooses the next step from the largest convective rate
+    (Solver.set_time_step_control, solver.time_step_next): want = target_courant / rate_max, held inside
+    [dt * max_shrink, dt * max_growth] and then inside [dt_min, dt_max], chosen anew after every interval-th step."""
+    _fields_ = [
+        ("target_courant", C.c_double), ("dt_min", C.c_double), ("dt_max", C.c_double), ("max_growth", C.c_double),
+        ("max_shrink", C.c_double), ("interval", C.c_uint64), ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+    ]
+
+    @classmethod
+    def make(cls, target_courant=None, dt_min=None, dt_max=None, **overrides):
+        """orc_time_step_control_default with the given fields replaced"""
+        from ._lib import lib
+        c = cls()
+        lib().orc_time_step_control_default(C.byref(c))
+        given = dict(overrides, target_courant=target_courant, dt_min=dt_min, dt_max=dt_max)
+        for k, v in given.items():
+            if v is None:
+                continue
+            if k not in dict(cls._fields_):
+                raise TypeError("TimeStepControl has no field %r" % k)
+            setattr(c, k, v)
+        return c
 
 
 class ScalarBc:  # include/orc_types.h OrcScalarBc

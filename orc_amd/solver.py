@@ -72,13 +72,42 @@ def solve_steady_converged(mesh, u, v, w, p, numerical_settings, rho, mu, conver
     return st, int(done.value), bool(conv.value), rec
 
 
+def time_step_next(control, dt, rate_max, raise_on_error=True):
+    """orc_time_step_next (host arithmetic, no device): the step that follows `dt` under a settings.TimeStepControl when the largest
+    convective rate is rate_max (with raise_on_error=False: (status, dt_next), dt_next None when refused)"""
+    out = C.c_double(0.0)
+    st = lib().orc_time_step_next(C.byref(control) if control is not None else None, C.c_double(dt), C.c_double(rate_max), C.byref(out))
+    if raise_on_error:
+        check(st)
+        return out.value
+    return st, (out.value if st == 0 else None)
+
+
 def solve_transient(mesh, u, v, w, p, settings, rho, mu, transient, time_steps, reporting_interval=0, report=None,
-                    raise_on_error=True):
+                    raise_on_error=True, control=None):
     """Implicit time stepping (orc_solve_transient): time_steps steps of `transient` (settings.Transient) from u, v, w, p,
     updated in place.  report(step, mean_velocity[3], peclet[3], velocity_correction, pressure_correction, ms_per_step)
-    with the last inner iteration's values."""
+    with the last inner iteration's values.  control (settings.TimeStepControl): the steps after the first are chosen by it
+    (Solver.set_time_step_control); the run then goes through a Solver, ms_per_step is 0 and the step history is returned
+    next to the status."""
     for a in (u, v, w, p):
         assert a.dtype == np.float64 and a.flags.c_contiguous and len(a) == mesh.n_cells
+    if control is not None:
+        s = Solver(mesh, settings, rho, mu)
+        s.set_fields(u, v, w, p)
+        st = s.set_transient(transient, raise_on_error=raise_on_error)
+        st = st or s.set_time_step_control(control, raise_on_error=raise_on_error)
+        for k in range(1, time_steps + 1):
+            if st != 0:
+                break
+            st, row = s.advance(1, report=True, raise_on_error=False)
+            if raise_on_error:
+                check(st)
+            if st == 0 and report is not None and reporting_interval and k % reporting_interval == 0:
+                report(k, tuple(row[0, 0:3]), tuple(row[0, 3:6]), row[0, 6], row[0, 7], 0.0)
+        for dst, src in zip((u, v, w, p), s.get_fields()):
+            dst[:] = src
+        return st, s.time_step_history()
     cb = None
     if report is not None:
         def _cb(it, mv, pe, vc, pc, ms, _user):
@@ -458,6 +487,70 @@ class Solver:
             check(st)
             return rep if report else st
         return (st, rep) if report else st
+
+    # ---------------------------------------------------------------- adaptive time stepping (orc_amd.h "adaptive time stepping")
+    def courant(self, field=False, raise_on_error=True):
+        """orc_solver_courant: (rate_max, cell[, rate]) — the largest convective rate sum_f |U_f . n| A / (2 V) of the current fields
+        (times dt: the Courant number), the smallest ORC id that attains it (-1 on a partitioned mesh) and, with field=True, the
+        per-cell rates in ORC order from the same launch (with raise_on_error=False the status comes first)"""
+        r, c = C.c_double(0.0), C.c_int64(-1)
+        rate = np.zeros(self.n) if field else None
+        st = lib().orc_solver_courant(self.ptr, C.byref(r), C.byref(c), _p(rate) if field else None)
+        out = (r.value, int(c.value), rate) if field else (r.value, int(c.value))
+        if raise_on_error:
+            check(st)
+            return out
+        return (st,) + out
+
+    def set_time_step(self, dt, raise_on_error=True):
+        """orc_solver_set_time_step: the step the next advance() takes; levels, time and history are kept"""
+        st = lib().orc_solver_set_time_step(self.ptr, C.c_double(dt))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def set_time_step_control(self, control=None, raise_on_error=True):
+        """orc_solver_set_time_step_control: a settings.TimeStepControl lets advance() choose its steps, None turns that off"""
+        st = lib().orc_solver_set_time_step_control(self.ptr, C.byref(control) if control is not None else None)
+        if raise_on_error:
+            check(st)
+        return st
+
+    def time_state(self):
+        """orc_solver_get_time_state: dict(time, dt_next, dt_last, dt_before_last)"""
+        v = [C.c_double(0.0) for _ in range(4)]
+        check(lib().orc_solver_get_time_state(self.ptr, *[C.byref(x) for x in v]))
+        return dict(zip(("time", "dt_next", "dt_last", "dt_before_last"), (x.value for x in v)))
+
+    def set_time_state(self, time, dt_last=None, dt_before_last=None, raise_on_error=True):
+        """orc_solver_set_time_state: the clock and the steps that led to the levels of set_time_levels (a restart); a dict from
+        time_state() is taken as well, its dt_next going to set_time_step"""
+        if isinstance(time, dict):
+            d = time
+            st = lib().orc_solver_set_time_state(self.ptr, C.c_double(d["time"]), C.c_double(d["dt_last"]), C.c_double(d["dt_before_last"]))
+            st = st or lib().orc_solver_set_time_step(self.ptr, C.c_double(d["dt_next"]))
+        else:
+            st = lib().orc_solver_set_time_state(self.ptr, C.c_double(time), C.c_double(dt_last),
+                                                 C.c_double(dt_last if dt_before_last is None else dt_before_last))
+        if raise_on_error:
+            check(st)
+        return st
+
+    def time_step_history(self, first=0, count=None):
+        """orc_solver_time_step_history: (k, 4) — time reached, dt used, rate_max at the step's end (NaN where it was not measured),
+        cell — one row per step while control is on or a manual step has been set"""
+        have = int(lib().orc_solver_time_step_count(self.ptr))
+        count = have - first if count is None else count
+        out = np.zeros((max(count, 0), 4))
+        check(lib().orc_solver_time_step_history(self.ptr, C.c_uint64(first), C.c_uint64(count), _p(out)))
+        return out
+
+    def bench_courant(self, reps=50):
+        """(ms of the Courant reduction, ms of derived_cell_k selecting the convective rate alone): HIP-event averages"""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        check(lib().orc_bench_courant(self.ptr, C.c_int(reps), C.byref(a)))
+        check(lib().orc_bench_derived_rate(self.ptr, C.c_int(reps), C.byref(b)))
+        return a.value, b.value
 
     # ---------------------------------------------------------------- a linear solver of its own for p' (orc_solver_set_pressure_solver)
     def set_pressure_solver(self, solver_type=None, preconditioner=1, iterations=50, threshold=0.0, relaxation=0.5, raise_on_error=True):
