@@ -965,6 +965,60 @@ int orc_poly_channel_write_msh(const char *path, int64_t nx, int64_t ny, int64_t
  * the 580 MB temporary file per rank that BASELINE configs[4] cost in r04.  NULL + *status on failure. */
 OrcMeshData *orc_mixed_channel_generate(int64_t nx, int64_t ny, int64_t nz, double lx, double ly, double lz, int polyhedra, int *status);
 
+/* ---------- cut surfaces (new-build extension, orc_types.h ORC_CUT_MAX_POINTS / OrcCutSkip) ----------
+ * Plane slices and iso-surfaces as polygons, built on the device from the mesh's node geometry (DESIGN.md §3 "Cut surfaces": every rule
+ * of the surface, bit for bit).  Opt-in and read-only: no entry changes a bit of a mesh's cell geometry or of a solver, and a solver that
+ * never asks for a cut launches what it launched before.
+ *  - orc_mesh_set_nodes: the arrays of orc_mesh_data_nodes.  Checked on the host (n_faces equal to the mesh's, every node id in
+ *    [0, n_vertices), at least 3 nodes per face, n_vertices < 2^31), uploaded once with 32-bit ids together with a node -> cell table
+ *    (per node the cells with a face through it, ascending ORC id) and kept by the mesh.  A later call is checked in the same way and
+ *    changes nothing; one that brings other sizes is refused.  The cells must be closed (every edge of a cell in exactly two of its
+ *    faces): otherwise a cell may emit fewer points than it was counted for, and the points it leaves are zero with key (0, 0) and join
+ *    the polygon before them — within bounds, uncounted.  A partitioned mesh is refused.
+ *  - orc_mesh_node_average: phi_v = (sum_c w_c phi_c) / (sum_c w_c), w_c = 1 / |x_c - x_v| over the node's cells in ascending ORC id;
+ *    cell values only, also at boundary nodes.
+ *  - orc_cut_plane: d_v = ((x - o.x) n.x + (y - o.y) n.y) + (z - o.z) n.z; the normal finite and not zero, any length.
+ *    orc_cut_node_level: d_v = node_values[v] - level.  orc_cut_cell_field: orc_mesh_node_average of cell_values (ORC order), then the
+ *    level.  orc_solver_cut_field: the same on the solver's own field (field_bit = 1u << one OrcProbeField) without leaving the device.
+ *    All four return NULL + *status on failure.  Destroy a cut before its mesh.
+ *  - orc_cut_sizes / orc_cut_get: polygons P, points NP, the cells skipped per OrcCutSkip; poly_ptr [P + 1] into the points, the owner
+ *    cell (ORC id) per polygon, points [3 NP] point-major, the key (lo, hi node id of the cut edge) per point, the area vector [3 P]
+ *    polygon-major.  Every output may be NULL; P = 0 is legal.  Polygons ascend in ORC cell id whatever the mesh's internal numbering.
+ *  - orc_solver_sample_cut: the fields of field_mask as orc_solver_sample_probes; ORC_PROBE_CELL: one value per polygon (the owner's),
+ *    field k at out[k * P + p]; ORC_PROBE_LINEAR: one per polygon vertex through the owner's gradient, field k at out[k * NP + i] - the
+ *    bits orc_solver_sample_probes gives for that cell and point.  Refusals and error codes are those of orc_solver_sample_probes.
+ *  - orc_cut_sample_cells: the CELL gather for n_fields host arrays of n_cells values each in ORC order, field k at out[k * P + p].
+ *  - orc_cut_limits: ORC_CUT_MAX_POINTS and the entries one workgroup of the scan takes.  Needs no device.
+ *  - orc_bench_cut: HIP-event average ms over `reps` of avg_ms[0] the node average of a cell field, [1] the classify pass with its
+ *    face pass, [2] the scan, [3] the emit (points, polygon table, area vectors) of the plane (origin, normal).
+ *  - orc_write_vtu_polygons: host only; VTK_POLYGON cells over poly_nodes [poly_ptr[n_polys]] (ids into points) with cell data (per
+ *    polygon) and point data (per point; every point must be used), in the conventions of orc_write_vtu_faces.
+ * Every compute entry looks for a device first (ORC_ERR_NO_DEVICE without one).  Refused with ORC_ERR_BAD_ARGUMENT, mesh and solver
+ * unchanged: a null handle or array; a zero or non-finite normal, a non-finite origin or level; a cut before orc_mesh_set_nodes; a cut of
+ * another mesh handed to a solver; a field_mask of 0 or with unknown bits, a field_bit that is not exactly one known bit; ORC_PROBE_PHI
+ * without the scalar arm; a partitioned mesh. */
+typedef struct OrcCut OrcCut;
+int orc_mesh_set_nodes(OrcMesh *m, int64_t n_vertices, const double *vertices /*[3V]*/, int64_t n_faces, const int64_t *face_node_ptr /*[F+1]*/,
+                       const int64_t *face_nodes);
+int orc_mesh_node_average(OrcMesh *m, const double *cell_values /*[n_cells] ORC order*/, double *node_values /*[V]*/);
+OrcCut *orc_cut_plane(OrcMesh *m, const double origin[3], const double normal[3], int *status);
+OrcCut *orc_cut_node_level(OrcMesh *m, const double *node_values /*[V]*/, double level, int *status);
+OrcCut *orc_cut_cell_field(OrcMesh *m, const double *cell_values /*[n_cells] ORC order*/, double level, int *status);
+OrcCut *orc_solver_cut_field(OrcSolver *s, uint32_t field_bit, double level, int *status);
+void orc_cut_destroy(OrcCut *cut);
+int orc_cut_sizes(const OrcCut *cut, int64_t *n_polygons, int64_t *n_points, int64_t *n_skipped_nonfinite, int64_t *n_skipped_overflow);
+int orc_cut_get(const OrcCut *cut, int64_t *poly_ptr /*[P+1]*/, int64_t *cell /*[P]*/, double *points /*[3 NP]*/, int64_t *key_lo /*[NP]*/,
+                int64_t *key_hi /*[NP]*/, double *area_vector /*[3P]*/);
+int orc_cut_limits(int32_t *max_points, int32_t *scan_chunk);
+int orc_solver_sample_cut(OrcSolver *s, const OrcCut *cut, uint32_t field_mask, int32_t interpolation, double *out);
+int orc_cut_sample_cells(const OrcCut *cut, int32_t n_fields, const double *fields /*[n_fields][n_cells] ORC order*/, double *out /*[n_fields][P]*/);
+int orc_bench_cut(OrcMesh *m, const double *cell_values /*[n_cells] ORC order*/, const double origin[3], const double normal[3], int reps,
+                  double avg_ms[4]);
+int orc_write_vtu_polygons(const char *path, int64_t n_points, const double *points /*[3 n_points]*/, int64_t n_polys, const int64_t *poly_ptr /*[n_polys + 1]*/,
+                           const int64_t *poly_nodes, int32_t n_cell_arrays, const char *const *cell_names, const int32_t *cell_components,
+                           const double *const *cell_data, int32_t n_point_arrays, const char *const *point_names, const int32_t *point_components,
+                           const double *const *point_data, int32_t encoding);
+
 /* ---------- multi-GPU (one process per GPU, RCCL over xGMI) ---------- */
 #define ORC_COMM_ID_BYTES 128
 int orc_comm_get_unique_id(unsigned char id[ORC_COMM_ID_BYTES]);          /* rank 0, then broadcast by the host launcher */

@@ -441,6 +441,14 @@ typedef struct OrcTracerSettings {
     double min_speed;      /* >= 0, LENGTH only */
 } OrcTracerSettings;       /* 32 bytes */
 
+/* Cut surfaces (new-build extension; orc_amd.h: orc_cut_plane, orc_cut_node_level, orc_cut_cell_field, orc_solver_cut_field): the
+ * polygons in which a level set of a node function d cuts the cells.  DESIGN.md §3 "Cut surfaces" fixes every rule. */
+#define ORC_CUT_MAX_POINTS 32 /* cut points one cell may carry; a cell with more is skipped and counted (OVERFLOW) */
+enum OrcCutSkip {
+    ORC_CUT_SKIP_NONFINITE = 0, /* a node of the cell has a d that is not finite */
+    ORC_CUT_SKIP_OVERFLOW = 1   /* more than ORC_CUT_MAX_POINTS cut points */
+};
+
 #ifdef __cplusplus
 }
 #endif

@@ -269,6 +269,38 @@ def lib():
             L.orc_bench_courant.restype = C.c_int
             L.orc_bench_derived_rate.argtypes = [C.c_void_p, C.c_int, _f64]
             L.orc_bench_derived_rate.restype = C.c_int
+        # cut surfaces (orc_amd.h "cut surfaces"): full signatures
+        if hasattr(L, "orc_cut_plane"):
+            _f64, _i64, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+            L.orc_mesh_set_nodes.argtypes = [C.c_void_p, C.c_int64, _f64, C.c_int64, _i64, _i64]
+            L.orc_mesh_set_nodes.restype = C.c_int
+            L.orc_mesh_node_average.argtypes = [C.c_void_p, _f64, _f64]
+            L.orc_mesh_node_average.restype = C.c_int
+            L.orc_cut_plane.argtypes = [C.c_void_p, _f64, _f64, C.POINTER(C.c_int)]
+            L.orc_cut_plane.restype = C.c_void_p
+            L.orc_cut_node_level.argtypes = [C.c_void_p, _f64, C.c_double, C.POINTER(C.c_int)]
+            L.orc_cut_node_level.restype = C.c_void_p
+            L.orc_cut_cell_field.argtypes = [C.c_void_p, _f64, C.c_double, C.POINTER(C.c_int)]
+            L.orc_cut_cell_field.restype = C.c_void_p
+            L.orc_solver_cut_field.argtypes = [C.c_void_p, C.c_uint32, C.c_double, C.POINTER(C.c_int)]
+            L.orc_solver_cut_field.restype = C.c_void_p
+            L.orc_cut_destroy.argtypes = [C.c_void_p]
+            L.orc_cut_destroy.restype = None
+            L.orc_cut_sizes.argtypes = [C.c_void_p, _i64, _i64, _i64, _i64]
+            L.orc_cut_sizes.restype = C.c_int
+            L.orc_cut_get.argtypes = [C.c_void_p, _i64, _i64, _f64, _i64, _i64, _f64]
+            L.orc_cut_get.restype = C.c_int
+            L.orc_cut_limits.argtypes = [_i32, _i32]
+            L.orc_cut_limits.restype = C.c_int
+            L.orc_solver_sample_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, _f64]
+            L.orc_solver_sample_cut.restype = C.c_int
+            L.orc_cut_sample_cells.argtypes = [C.c_void_p, C.c_int32, _f64, _f64]
+            L.orc_cut_sample_cells.restype = C.c_int
+            L.orc_bench_cut.argtypes = [C.c_void_p, _f64, _f64, _f64, C.c_int, _f64]
+            L.orc_bench_cut.restype = C.c_int
+            _tables = [C.c_int32, C.POINTER(C.c_char_p), _i32, C.POINTER(_f64)]
+            L.orc_write_vtu_polygons.argtypes = [C.c_char_p, C.c_int64, _f64, C.c_int64, _i64, _i64] + _tables + _tables + [C.c_int32]
+            L.orc_write_vtu_polygons.restype = C.c_int
         # the set-up's statistics (orc_amd.h "orc_debug_amg_setup_stats")
         if hasattr(L, "orc_debug_amg_setup_stats"):
             L.orc_debug_amg_setup_stats.argtypes = [C.POINTER(C.c_longlong), C.c_int]

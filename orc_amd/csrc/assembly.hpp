@@ -61,6 +61,16 @@ struct ProbeTiles {
     DevBuf<int32_t> orc_id;   // [n_cells] ORC id of every internal cell; empty when the numbering is ORC's own
 };
 
+// The node geometry of a mesh (cut.hip, orc_mesh_set_nodes): the device mesh itself holds no vertex, so a cut needs the vertices, the
+// faces' node cycles and, for the node average of a cell field, the cells around every node.  Uploaded once, kept as long as the mesh.
+struct CutNodes {
+    int64_t n_vertices = 0, n_face_nodes = 0, n_node_cells = 0;
+    DevBuf<double> vx, vy, vz;          // [V]
+    DevBuf<int32_t> fnp, fn;            // [F + 1] into fn; the node cycle of every face
+    DevBuf<int32_t> ncp, nc;            // [V + 1] into nc; per node the cells (internal numbering) with a face through it, ascending ORC id
+    DevBuf<int32_t> orc2int, int2orc;   // [n_cells] each; both empty when the numbering is ORC's own
+};
+
 #ifdef __HIPCC__
 // the TVD limiters of settings::MomentumDiscretization (lib.rs:107-118): momentum_k and the scalar arm's scalar_face_k
 __device__ __forceinline__ double psi_eval(int momentum, double r) {
@@ -98,6 +108,7 @@ struct OrcMesh {
     std::unique_ptr<orc::SurfaceIndex> surface;  // null until the first surface report (surface.hip)
     std::unique_ptr<orc::WallDistance> wall;     // null until the first wall distance (wall_distance.hip)
     std::unique_ptr<orc::ProbeTiles> probe_tiles;  // null until the first probe set (probes.hip)
+    std::unique_ptr<orc::CutNodes> nodes;          // null until orc_mesh_set_nodes (cut.hip)
     orc::MeshDev dev() const;
 };
 

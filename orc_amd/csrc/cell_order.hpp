@@ -10,7 +10,8 @@
 //             orc_surface_integrals and orc_boundary_fields, orc_solver_get_statistics / set_statistics_state, and the cell ids of
 //             orc_probes_get and orc_tracers_get, the labels into orc_cell_groups_create, the cell ids of orc_cell_groups_get, the
 //             fields into orc_group_integrals and the `where` cells of every group report (orc_solver_group_report / _statistics /
-//             _history, orc_group_integrals), the cell and the per-cell rates of orc_solver_courant
+//             _history, orc_group_integrals), the cell and the per-cell rates of orc_solver_courant, the cell values into orc_mesh_node_average / orc_cut_cell_field /
+//             orc_cut_sample_cells and the owner cells of orc_cut_get
 //   internalorc_mesh_matrix_pattern, the matrix values and right-hand sides of orc_solver_assemble_momentum / _pressure / _scalar,
 //             orc_solver_get_diffusion, orc_solver_get_pressure_rhs, orc_build_momentum_diffusion_matrix, orc_initialize_momentum_matrix
 //             (orc_mesh_cell_order reports g)

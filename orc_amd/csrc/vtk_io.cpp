@@ -154,10 +154,23 @@ struct Writer {
     }
 };
 
-// renumber the used points ascending, then write the file; the arrays are cell data of n_items cells, or (point_data, every point
-// used) point data of n_points points
-int finish(const char *path, int64_t n_points, const double *points, Piece &P, const Arrays &A, int64_t n_items, int32_t encoding,
-           bool point_data = false) {
+// one <CellData> or <PointData> section: structure-of-arrays by component -> VTK's tuples
+void data_section(Writer &W, const char *tag, const Arrays &A, int64_t n_items) {
+    fprintf(W.f, "      <%s>\n", tag);
+    std::vector<double> tuples;
+    for (int32_t a = 0; a < A.n; ++a) {
+        const int32_t k = A.components[a];
+        tuples.resize((size_t)k * (size_t)n_items);
+        for (int32_t q = 0; q < k; ++q)
+            for (int64_t c = 0; c < n_items; ++c) tuples[(size_t)c * k + q] = A.data[a][(size_t)q * n_items + c];
+        W.array("Float64", A.names[a], k, tuples, "%.17g");
+    }
+    fprintf(W.f, "      </%s>\n", tag);
+}
+
+// renumber the used points ascending, then write the file; C: cell data of the n_items cells (null: no section), Pt: point data of the
+// n_points points, every one of which the piece must use (null: no section)
+int finish(const char *path, int64_t n_points, const double *points, Piece &P, const Arrays *C, const Arrays *Pt, int64_t n_items, int32_t encoding) {
     std::vector<int64_t> new_id((size_t)n_points, -1);
     for (int64_t v : P.connectivity) new_id[(size_t)v] = 0;
     if (P.any_polyhedron)
@@ -202,17 +215,10 @@ int finish(const char *path, int64_t n_points, const double *points, Piece &P, c
         W.array("Int64", "faces", 0, P.faces, "%lld");
         W.array("Int64", "faceoffsets", 0, P.faceoffsets, "%lld");
     }
-    fprintf(f, "      </Cells>\n      <%s>\n", point_data ? "PointData" : "CellData");
-    if (point_data) n_items = used;
-    std::vector<double> tuples;
-    for (int32_t a = 0; a < A.n; ++a) {  // structure-of-arrays by component -> VTK's tuples
-        const int32_t k = A.components[a];
-        tuples.resize((size_t)k * (size_t)n_items);
-        for (int32_t q = 0; q < k; ++q)
-            for (int64_t c = 0; c < n_items; ++c) tuples[(size_t)c * k + q] = A.data[a][(size_t)q * n_items + c];
-        W.array("Float64", A.names[a], k, tuples, "%.17g");
-    }
-    fprintf(f, "      </%s>\n    </Piece>\n  </UnstructuredGrid>\n", point_data ? "PointData" : "CellData");
+    fprintf(f, "      </Cells>\n");
+    if (Pt) data_section(W, "PointData", *Pt, used);
+    if (C) data_section(W, "CellData", *C, n_items);
+    fprintf(f, "    </Piece>\n  </UnstructuredGrid>\n");
     if (W.raw) {
         fprintf(f, "  <AppendedData encoding=\"raw\">\n_");
         for (const std::vector<char> &blk : W.appended) {
@@ -283,7 +289,7 @@ int orc_write_vtu(const char *path, int64_t n_points, const double *points, int6
         }
         P.offsets.push_back((int64_t)P.connectivity.size());
     }
-    return finish(path, n_points, points, P, A, n_cells, encoding);
+    return finish(path, n_points, points, P, &A, nullptr, n_cells, encoding);
 }
 
 int orc_write_vtu_faces(const char *path, int64_t n_points, const double *points, int64_t n_faces, const int64_t *face_ids,
@@ -301,7 +307,7 @@ int orc_write_vtu_faces(const char *path, int64_t n_points, const double *points
         P.offsets.push_back((int64_t)P.connectivity.size());
         P.types.push_back(kVtkPolygon);
     }
-    return finish(path, n_points, points, P, A, n_faces, encoding);
+    return finish(path, n_points, points, P, &A, nullptr, n_faces, encoding);
 }
 
 int orc_write_vtu_lines(const char *path, int64_t n_lines, const int64_t *line_ptr, const double *points, int32_t n_arrays, const char *const *names,
@@ -320,7 +326,36 @@ int orc_write_vtu_lines(const char *path, int64_t n_lines, const int64_t *line_p
         P.offsets.push_back(line_ptr[i + 1]);
         P.types.push_back(line_ptr[i + 1] - line_ptr[i] == 1 ? kVtkVertex : kVtkPolyLine);
     }
-    return finish(path, n_points, points, P, A, n_lines, encoding, true);
+    return finish(path, n_points, points, P, nullptr, &A, n_lines, encoding);
+}
+
+int orc_write_vtu_polygons(const char *path, int64_t n_points, const double *points, int64_t n_polys, const int64_t *poly_ptr, const int64_t *poly_nodes,
+                           int32_t n_cell_arrays, const char *const *cell_names, const int32_t *cell_components, const double *const *cell_data,
+                           int32_t n_point_arrays, const char *const *point_names, const int32_t *point_components, const double *const *point_data,
+                           int32_t encoding) {
+    if (!path || n_points < 0 || n_polys < 0 || !poly_ptr || (n_points > 0 && !points)) return set_error(ORC_ERR_BAD_ARGUMENT, "write_vtu_polygons: null or negative argument");
+    Arrays C{n_cell_arrays, cell_names, cell_components, cell_data}, Pt{n_point_arrays, point_names, point_components, point_data};
+    ORC_TRY(check_arrays(C, encoding));
+    ORC_TRY(check_arrays(Pt, encoding));
+    if (poly_ptr[0] != 0) return set_error(ORC_ERR_BAD_ARGUMENT, "write_vtu_polygons: poly_ptr must start at 0");
+    for (int64_t i = 0; i < n_polys; ++i)
+        if (poly_ptr[i + 1] - poly_ptr[i] < 3) return set_error(ORC_ERR_BAD_ARGUMENT, "write_vtu_polygons: polygon %lld has fewer than 3 nodes", (long long)i);
+    if (n_polys > 0 && !poly_nodes) return set_error(ORC_ERR_BAD_ARGUMENT, "write_vtu_polygons: null connectivity");
+    std::vector<char> used((size_t)n_points, 0);
+    Piece P;
+    for (int64_t i = 0; i < n_polys; ++i) {
+        for (int64_t q = poly_ptr[i]; q < poly_ptr[i + 1]; ++q) {
+            const int64_t v = poly_nodes[q];
+            if (v < 0 || v >= n_points) return set_error(ORC_ERR_BAD_ARGUMENT, "write_vtu_polygons: polygon %lld names point %lld of %lld", (long long)i, (long long)v, (long long)n_points);
+            used[(size_t)v] = 1;
+            P.connectivity.push_back(v);
+        }
+        P.offsets.push_back(poly_ptr[i + 1]);
+        P.types.push_back(kVtkPolygon);
+    }
+    for (int64_t v = 0; v < n_points; ++v)  // point data is written per point of the file: none may drop out
+        if (!used[(size_t)v]) return set_error(ORC_ERR_BAD_ARGUMENT, "write_vtu_polygons: point %lld belongs to no polygon", (long long)v);
+    return finish(path, n_points, points, P, &C, &Pt, n_polys, encoding);
 }
 
 }  // extern "C"

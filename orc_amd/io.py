@@ -190,3 +190,27 @@ def write_vtu_lines(path, lines, point_data=None, encoding="raw"):
     keep, k, names, comps, data = _vtu_tables(point_data or {}, int(ptr[-1]))
     check(lib().orc_write_vtu_lines(str(path).encode(), C.c_int64(len(lines)), _p(ptr, _I64), _p(pts), C.c_int32(k), names, comps, data,
                                     C.c_int32(_ENCODINGS[encoding])))
+
+
+def write_vtu_cut(path, cut, cell_data=None, point_data=None, encoding="raw", per="vertex"):
+    """orc_write_vtu_polygons: the welded surface of a mesh.Cut as VTK_POLYGON cells.  cell_data {name: ndarray[P] or [P, k]} per polygon.
+    point_data with per="vertex" (the default): {name: ndarray[NP] or [NP, k]} per polygon vertex (Solver.sample_cut(..., "linear")); a
+    point takes the value of its first occurrence, i.e. the first polygon in order wins — LINEAR values of one point are bit-identical
+    only within one cell.  per="point": {name: ndarray[M] or [M, k]} per welded point, in the order of cut.welded()."""
+    if per not in ("vertex", "point"):
+        raise ValueError("write_vtu_cut: per must be 'vertex' or 'point'")
+    pts, nodes, first = cut.welded()
+    ptr = np.ascontiguousarray(cut.poly_ptr, np.int64)
+    pd = {}
+    for name, a in (point_data or {}).items():
+        a = np.asarray(a, dtype=np.float64)
+        if per == "vertex":
+            if len(a) != cut.n_points:
+                raise ValueError("array '%s': per='vertex' needs one value per polygon vertex (%d), got %d" % (name, cut.n_points, len(a)))
+            a = a[first]
+        pd[name] = a
+    keep_c, kc, names_c, comps_c, data_c = _vtu_tables(cell_data or {}, cut.n_polygons)
+    keep_p, kp, names_p, comps_p, data_p = _vtu_tables(pd, len(pts))
+    pts = np.ascontiguousarray(pts)
+    check(lib().orc_write_vtu_polygons(str(path).encode(), C.c_int64(len(pts)), _p(pts), C.c_int64(cut.n_polygons), _p(ptr, _I64), _p(nodes, _I64),
+                                       C.c_int32(kc), names_c, comps_c, data_c, C.c_int32(kp), names_p, comps_p, data_p, C.c_int32(_ENCODINGS[encoding])))

@@ -92,6 +92,34 @@ def hex_channel(nx, ny, nz, lx=0.002, ly=0.001, lz=None):
     return a
 
 
+def hex_channel_nodes(a, nx, ny, nz, lx=0.002, ly=0.001, lz=None):
+    """Node geometry for the arrays of hex_channel(nx, ny, nz, ...), which carry none: (vertices [V, 3], face_node_ptr, face_nodes) as
+    MeshData.nodes() returns them, rebuilt from the lattice — a face's four nodes are its centroid plus and minus half a cell in its two
+    tangential directions, node (i, j, k) has id (k (ny + 1) + j)(nx + 1) + i.  The winding of a cycle is not the file's; the cuts derive
+    the orientation from the geometry, so either serves (Mesh.set_nodes)."""
+    if lz is None:
+        lz = 1e-4 * nz
+    h = np.array([lx / nx, ly / ny, lz / nz])
+    n1 = np.array([nx + 1, ny + 1, nz + 1])
+    k, j, i = np.meshgrid(np.arange(n1[2]), np.arange(n1[1]), np.arange(n1[0]), indexing="ij")
+    vert = np.stack([i.ravel() * h[0], j.ravel() * h[1], k.ravel() * h[2]], axis=1)
+    fc, fn = np.asarray(a["face_centroid"]), np.asarray(a["face_normal"])
+    axis = np.argmax(np.abs(fn), axis=1)
+    F = len(fc)
+    nodes = np.zeros((F, 4), np.int64)
+    for ax in range(3):
+        sel = np.where(axis == ax)[0]
+        t1, t2 = [q for q in range(3) if q != ax]
+        base = np.rint(fc[sel] / h[None, :] * 2).astype(np.int64)  # twice the lattice coordinate: even along the axis, odd across
+        for q, (s1, s2) in enumerate([(-1, -1), (1, -1), (1, 1), (-1, 1)]):
+            ijk = base.copy()
+            ijk[:, t1] += s1
+            ijk[:, t2] += s2
+            ijk //= 2
+            nodes[sel, q] = (ijk[:, 2] * n1[1] + ijk[:, 1]) * n1[0] + ijk[:, 0]
+    return vert, np.arange(F + 1, dtype=np.int64) * 4, nodes.reshape(-1)
+
+
 def write_hex_channel_msh(path, nx, ny, nz, lx=0.002, ly=0.001, lz=None):
     if lz is None:
         lz = 1e-4 * nz
@@ -358,12 +386,98 @@ class Tracers:
         return self.status == 0
 
 
+def cut_limits():
+    """orc_cut_limits -> dict(max_points, scan_chunk): the cut points one cell may carry (ORC_CUT_MAX_POINTS) and the entries one
+    workgroup of the scan takes.  Needs no device."""
+    a, b = C.c_int32(0), C.c_int32(0)
+    check(lib().orc_cut_limits(C.byref(a), C.byref(b)))
+    return dict(max_points=int(a.value), scan_chunk=int(b.value))
+
+
+class Cut:
+    """A cut surface (OrcCut*), kept on the device: the polygons of Mesh.slice / cut_nodes / isosurface and Solver.isosurface, in
+    ascending ORC cell id.  poly_ptr [P + 1] into the points; cell [P] the owner (ORC id); points [NP, 3]; keys [NP, 2] the (lo, hi)
+    node ids of every point's cut edge; area_vector [P, 3]; area [P] its length; skipped = dict(nonfinite, overflow), the cells left
+    out and why.  Each array is read from the device when first asked for."""
+
+    def __init__(self, mesh, ptr, status):
+        check(status)
+        self.mesh = mesh  # keeps the mesh alive: a cut goes before its mesh
+        self.ptr = C.c_void_p(ptr)
+        v = [C.c_int64(0) for _ in range(4)]
+        check(lib().orc_cut_sizes(self.ptr, *[C.byref(x) for x in v]))
+        self.n_polygons, self.n_points = int(v[0].value), int(v[1].value)
+        self.skipped = dict(nonfinite=int(v[2].value), overflow=int(v[3].value))
+        self._got = None
+
+    def __del__(self):
+        if getattr(self, "ptr", None):
+            lib().orc_cut_destroy(self.ptr)
+            self.ptr = None
+
+    def __len__(self):
+        return self.n_polygons
+
+    def _get(self):
+        if self._got is None:
+            P, NP = self.n_polygons, self.n_points
+            g = dict(poly_ptr=np.zeros(P + 1, np.int64), cell=np.zeros(P, np.int64), points=np.zeros((NP, 3)), lo=np.zeros(NP, np.int64),
+                     hi=np.zeros(NP, np.int64), area_vector=np.zeros((P, 3)))
+            check(lib().orc_cut_get(self.ptr, g["poly_ptr"].ctypes.data_as(_I64), g["cell"].ctypes.data_as(_I64), g["points"].ctypes.data_as(_F64),
+                                    g["lo"].ctypes.data_as(_I64), g["hi"].ctypes.data_as(_I64), g["area_vector"].ctypes.data_as(_F64)))
+            g["keys"] = np.stack([g.pop("lo"), g.pop("hi")], axis=1)
+            self._got = g
+        return self._got
+
+    poly_ptr = property(lambda self: self._get()["poly_ptr"])
+    cell = property(lambda self: self._get()["cell"])
+    points = property(lambda self: self._get()["points"])
+    keys = property(lambda self: self._get()["keys"])
+    area_vector = property(lambda self: self._get()["area_vector"])
+
+    @property
+    def area(self):
+        a = self.area_vector
+        return np.sqrt((a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2])
+
+    def welded(self):
+        """-> (points [M, 3], nodes [NP], first [M]): the unique points by key in ascending (lo, hi), the polygon connectivity
+        (poly_ptr indexes it) and, per unique point, its first occurrence among the polygon vertices.  A key gives the same bits in every
+        cell that shares its edge, so any occurrence serves."""
+        k = self.keys
+        if len(k) == 0:
+            return np.zeros((0, 3)), np.zeros(0, np.int64), np.zeros(0, np.int64)
+        _, first, nodes = np.unique(k, axis=0, return_index=True, return_inverse=True)
+        return self.points[first], np.asarray(nodes, np.int64).reshape(-1), np.asarray(first, np.int64)
+
+    def integrate(self, per_polygon_vectors):
+        """sum over the polygons of v . A on the host, polygon by polygon in order: ((v.x A.x + v.y A.y) + v.z A.z) accumulated left to
+        right.  per_polygon_vectors [P, 3], e.g. rho (u, v, w) from Solver.sample_cut(cut, "uvw", "cell") for the mass flow."""
+        v = np.asarray(per_polygon_vectors, dtype=np.float64).reshape(-1, 3)
+        a = self.area_vector
+        if len(v) != len(a):
+            raise ValueError("integrate: one vector per polygon (%d), got %d" % (len(a), len(v)))
+        total = 0.0
+        for t in ((v[:, 0] * a[:, 0] + v[:, 1] * a[:, 1]) + v[:, 2] * a[:, 2]).tolist():
+            total = total + t
+        return total
+
+    def sample_cells(self, fields):
+        """orc_cut_sample_cells: {name: ndarray[n_cells] in ORC order} -> {name: ndarray[P]}, every polygon its owner cell's value"""
+        names = list(fields)
+        n = self.mesh.n_cells
+        src = np.ascontiguousarray(np.stack([np.asarray(fields[k], dtype=np.float64).reshape(n) for k in names]))
+        out = np.zeros((len(names), self.n_polygons))
+        check(lib().orc_cut_sample_cells(self.ptr, C.c_int32(len(names)), src.ctypes.data_as(_F64), out.ctypes.data_as(_F64)))
+        return {k: out[q] for q, k in enumerate(names)}
+
+
 class Mesh:
     """Device-resident mesh (OrcMesh*)."""
 
-    def __init__(self, arrays, ordering=None):
+    def __init__(self, arrays, ordering=None, nodes=None):
         """ordering: None = ORC's numbering; 1 = RCM, 2 = geometric (orc_mesh_create_reordered: internal renumbering,
-        fields still in ORC order)."""
+        fields still in ORC order).  nodes: a MeshData (or its nodes() tuple) for set_nodes()."""
         a = arrays
         self.arrays = a
         self._keep = [_i64(a["face_c0"]), _i64(a["face_c1"]), _i32(a["face_zone"]), _f64(a["face_area"]),
@@ -386,6 +500,9 @@ class Mesh:
         self._keep = None
         self.n_cells = lib().orc_mesh_n_cells(self.ptr)
         self.nnz = lib().orc_mesh_nnz(self.ptr)
+        self.n_vertices = 0
+        if nodes is not None:
+            self.set_nodes(nodes)
 
     def __del__(self):
         if getattr(self, "ptr", None):
@@ -469,6 +586,57 @@ class Mesh:
     def box_cells(self, lo, hi):
         """The cells whose centroid lies in the box lo <= x < hi (per coordinate, box_ids) -> a CellGroups of one group"""
         return CellGroups(self, box_ids(self.arrays["cell_centroid"], lo, hi), 1)
+
+    def set_nodes(self, mesh_data):
+        """orc_mesh_set_nodes: the node geometry (a MeshData, or the tuple its nodes() returns) onto the device, once per mesh: what
+        every cut and node_average() need.  A partitioned mesh is refused."""
+        vert, fnp, fn = mesh_data.nodes() if hasattr(mesh_data, "nodes") else mesh_data
+        vert, fnp, fn = _f64(np.asarray(vert).reshape(-1, 3)), _i64(fnp), _i64(fn)
+        check(lib().orc_mesh_set_nodes(self.ptr, C.c_int64(len(vert)), vert.ctypes.data_as(_F64), C.c_int64(len(fnp) - 1), fnp.ctypes.data_as(_I64),
+                                       fn.ctypes.data_as(_I64)))
+        self.n_vertices = len(vert)
+
+    def node_average(self, x):
+        """orc_mesh_node_average: the cell field x (ORC order) at the nodes, inverse-distance weighted over the cells around each node
+        (cell values only, also at boundary nodes) -> ndarray[V]"""
+        x = _f64(np.asarray(x, dtype=np.float64).reshape(self.n_cells))
+        out = np.zeros(self.n_vertices)
+        check(lib().orc_mesh_node_average(self.ptr, x.ctypes.data_as(_F64), out.ctypes.data_as(_F64)))
+        return out
+
+    def slice(self, origin, normal):
+        """orc_cut_plane: the polygons in which the plane through `origin` with `normal` (any length) cuts the cells -> Cut"""
+        o, n = _f64(np.asarray(origin, dtype=np.float64).reshape(3)), _f64(np.asarray(normal, dtype=np.float64).reshape(3))
+        st = C.c_int(0)
+        ptr = lib().orc_cut_plane(self.ptr, o.ctypes.data_as(_F64), n.ctypes.data_as(_F64), C.byref(st))
+        return Cut(self, ptr, st.value)
+
+    def cut_nodes(self, values, level=0.0):
+        """orc_cut_node_level: the surface values = level of any function given at the nodes [V] -> Cut"""
+        v = _f64(np.asarray(values, dtype=np.float64).reshape(-1))
+        if len(v) != self.n_vertices:
+            raise ValueError("cut_nodes: one value per node (%d), got %d" % (self.n_vertices, len(v)))
+        st = C.c_int(0)
+        ptr = lib().orc_cut_node_level(self.ptr, v.ctypes.data_as(_F64), C.c_double(level), C.byref(st))
+        return Cut(self, ptr, st.value)
+
+    def isosurface(self, cell_values, level):
+        """orc_cut_cell_field: node_average() of a cell field (ORC order), then its level -> Cut"""
+        x = _f64(np.asarray(cell_values, dtype=np.float64).reshape(-1))
+        if len(x) != self.n_cells:
+            raise ValueError("isosurface: one value per cell (%d), got %d" % (self.n_cells, len(x)))
+        st = C.c_int(0)
+        ptr = lib().orc_cut_cell_field(self.ptr, x.ctypes.data_as(_F64), C.c_double(level), C.byref(st))
+        return Cut(self, ptr, st.value)
+
+    def bench_cut(self, cell_values, origin, normal, reps=5):
+        """orc_bench_cut: HIP-event ms of (node average, classify, scan, emit) for the plane (origin, normal)"""
+        x = _f64(np.asarray(cell_values, dtype=np.float64).reshape(self.n_cells))
+        o, n = _f64(np.asarray(origin, dtype=np.float64).reshape(3)), _f64(np.asarray(normal, dtype=np.float64).reshape(3))
+        ms = np.zeros(4)
+        check(lib().orc_bench_cut(self.ptr, x.ctypes.data_as(_F64), o.ctypes.data_as(_F64), n.ctypes.data_as(_F64), C.c_int(reps),
+                                  ms.ctypes.data_as(_F64)))
+        return tuple(float(t) for t in ms)
 
     def seed(self, points):
         """orc_tracers_create: tracer particles at the points [n, 3], located as locate() locates them -> Tracers.  Seeds outside the

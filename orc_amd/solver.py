@@ -1034,6 +1034,30 @@ class Solver:
             return halves[0]
         return [np.concatenate([b[:0:-1], f]) for b, f in zip(*halves)]
 
+    def isosurface(self, field, level):
+        """orc_solver_cut_field: the surface field = level of one of the solver's own fields (a PROBE_NAMES name) without leaving the
+        device: the node average of Mesh.node_average, then the level -> mesh.Cut.  Needs Mesh.set_nodes().  Reads only."""
+        from .mesh import Cut
+        bit = 1 << PROBE_NAMES.index(field) if isinstance(field, str) else int(field)
+        st = C.c_int(0)
+        ptr = lib().orc_solver_cut_field(self.ptr, C.c_uint32(bit & 0xFFFFFFFF), C.c_double(level), C.byref(st))
+        return Cut(self.mesh, ptr, st.value)
+
+    def sample_cut(self, cut, fields=("u", "v", "w", "p"), interpolation="cell", raise_on_error=True):
+        """orc_solver_sample_cut: {name: ndarray} of the fields on a mesh.Cut; 'cell': one value per polygon (the owner cell's),
+        'linear': one per polygon vertex through the owner's gradient, the bits sample() gives for that cell and point.  Reads only.
+        (raise_on_error=False: (status, dict))"""
+        mask, names = _mask_of(fields, PROBE_NAMES)
+        n = 0 if cut is None else (cut.n_points if _interpolation(interpolation) == 1 else cut.n_polygons)
+        out = np.zeros((max(bin(mask).count("1"), 1), n))
+        st = lib().orc_solver_sample_cut(self.ptr, cut.ptr if cut is not None else None, C.c_uint32(mask & 0xFFFFFFFF),
+                                         C.c_int32(_interpolation(interpolation)), _p(out))
+        res = _probe_rows(out, mask, names) if st == 0 else {}
+        if raise_on_error:
+            check(st)
+            return res
+        return st, res
+
     def sample_tracers(self, tracers, fields=("u", "v", "w", "p"), interpolation="linear", raise_on_error=True):
         """orc_solver_sample_tracers: sample() at the particles' present positions and cells -> {name: ndarray[len(tracers)]}"""
         mask, names = _mask_of(fields, PROBE_NAMES)
