@@ -3,6 +3,7 @@
 #include <memory>
 
 #include "linalg.hpp"
+#include "postproc_state.hpp"
 
 namespace orc {
 
@@ -230,9 +231,8 @@ struct SolverState {
         DevBuf<int64_t> part_id;      // [kMaxPartials] their ORC ids
         DevBuf<int32_t> orc_id;       // ORC id of every internal cell; empty when the numbering is ORC's own
         DevBuf<int> status;
-        double *raw = nullptr;        // [2] pinned: where the pair lands
+        PinnedBuf<double> raw;        // [2] where the pair lands
         bool ready = false;
-        ~Courant() { if (raw) (void)hipHostFree(raw); }
     } cr;
     bool diagonals_assembled = false;  // k_momentum has written du/dv/dw at least once (Rhie-Chow face fluxes need them)
     // Residual monitors (orc_solver_set_monitors, residuals.hip): off unless enabled.  The partial sums and the folded raw slots are
@@ -244,7 +244,7 @@ struct SolverState {
         bool on = false;
         DevBuf<double> partials;   // [12 * kMaxPartials] momentum pass, then [3 * kMaxPartials] imbalance pass
         DevBuf<double> dev;        // [kSums + kMaxima]
-        double *raw = nullptr;     // [kSums + kMaxima], hipHostMalloc
+        PinnedBuf<double> raw;     // [kSums + kMaxima]
         std::vector<double> history;  // ORC_RESIDUAL_N doubles per monitored iteration
         uint64_t seen = 0;         // monitored iterations since monitoring was switched on
         double scale = 0.;         // the continuity scale (record slot 15)
@@ -297,105 +297,11 @@ struct SolverState {
         OrcWallDamping wd{ORC_WALL_DAMPING_NONE, 0, 0.41, 26., 0.};  // wall damping of the Smagorinsky length (orc_solver_set_wall_damping); mode NONE = off
     } vis;
     const double *cell_viscosity() const { return vis.on ? vis.mu.p : nullptr; }  // what the surface reports and boundary maps take
-    // Running time statistics (orc_solver_set_time_statistics, time_stats.hip): off unless enabled, every buffer allocated by the set
-    // call.  Reads the fields, never writes them; snapshot / restore leave it alone.
-    struct TimeStats {
-        bool on = false;
-        OrcTimeStatistics c{};
-        uint32_t field_mask = 0;  // OrcStatField bits of the enabled groups
-        int n_fields = 0;         // K = popcount(field_mask)
-        DevBuf<double> acc;       // [K][n] SoA, enabled fields in enum order, internal cell order; ghost entries stay 0
-        int64_t nb = 0;           // boundary faces (BOUNDARY group), else 0
-        DevBuf<double> bnd, bnd_now;  // [5][nb]: the means, and the maps of the state being sampled
-        DevBuf<int> bnd_status;   // boundary_map_k's status word
-        double W = 0.;            // sum of the weights
-        uint64_t samples = 0, step = 0;  // samples taken; orc_solver_advance steps since the arm was enabled
-    } ts;
-    // Probe history (orc_solver_set_probe_history, probes.hip): off unless enabled.  A record is sampled on the device into `rec`,
-    // copied to the pinned `raw` behind it and marked by `copied`; it joins the history at the next step, at a history call or when the
-    // arm goes off — by then the step's last synchronisation has long completed the copy.  Reads the fields, never writes them;
-    // snapshot / restore leave it alone.
-    struct ProbeHistory {
-        bool on = false;
-        const OrcProbes *probes = nullptr;
-        uint32_t mask = 0;
-        int32_t interpolation = 0;
-        int n_fields = 0;
-        uint64_t interval = 1, step = 0;  // orc_solver_advance steps since the arm was enabled
-        DevBuf<double> rec;               // [n_fields][n_points], the points in the probe set's device order
-        DevBuf<int> status;               // probe_sample_k's status word
-        double *raw = nullptr;            // [n_fields * n_points + 1] pinned: the record, then the status word as a double
-        hipEvent_t copied = nullptr;
-        bool pending = false;             // raw is on its way
-        double pending_time = 0.;
-        std::vector<double> times, values;  // k records: the time slots, and k * n_fields * n_points values in the caller's point order
-        ProbeHistory() = default;
-        ProbeHistory(const ProbeHistory &) = delete;
-        ProbeHistory &operator=(const ProbeHistory &) = delete;
-        ~ProbeHistory() { clear(); }
-        void clear() {
-            if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
-            if (raw) (void)hipHostFree(raw);
-            copied = nullptr; raw = nullptr;
-            rec.release(); status.release();
-            on = false; pending = false; probes = nullptr; mask = 0; n_fields = 0; step = 0;
-            times.clear(); values.clear();
-        }
-    } ph;
-    // Group history (orc_solver_set_group_history, groups.hip): off unless enabled.  The probe history's scheme: a record [G][1 + 6 F] is
-    // reduced on the device into `rec`, copied to the pinned `raw` behind it and marked by `copied`; it joins the history at the next
-    // step, at a history call or when the arm goes off.  Reads the fields, never writes them; snapshot / restore leave it alone.
-    struct GroupHistory {
-        bool on = false;
-        OrcCellGroups *groups = nullptr;
-        uint32_t mask = 0;
-        int32_t weighting = 0;
-        int n_fields = 0;
-        uint64_t interval = 1, step = 0;  // orc_solver_advance steps since the arm was enabled
-        DevBuf<double> rec;               // one record as group_fold_k writes it
-        double *raw = nullptr;            // the same, pinned
-        hipEvent_t copied = nullptr;
-        bool pending = false;             // raw is on its way
-        double pending_time = 0.;
-        std::vector<double> w_of;         // [G] the weight sums W: the group set's and the weighting's, the same in every record
-        std::vector<double> times, values;  // k records: the time slots, and k records as the device wrote them
-        GroupHistory() = default;
-        GroupHistory(const GroupHistory &) = delete;
-        GroupHistory &operator=(const GroupHistory &) = delete;
-        ~GroupHistory() { clear(); }
-        void clear() {
-            if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
-            if (raw) (void)hipHostFree(raw);
-            copied = nullptr; raw = nullptr;
-            rec.release();
-            on = false; pending = false; groups = nullptr; mask = 0; n_fields = 0; step = 0;
-            w_of.clear(); times.clear(); values.clear();
-        }
-    } gh;
-    // Tracer tracking (orc_solver_set_tracer_tracking, tracers.hip): off unless enabled.  Every step of orc_solver_advance moves the set
-    // by `substeps` substeps of dt / substeps (the step just taken) in the new velocity; the kernel's status word is copied to the pinned `raw` behind it and looked at
-    // by the next step.  Reads the fields, never writes them; snapshot / restore leave the set alone.
-    struct TracerTracking {
-        bool on = false;
-        OrcTracers *set = nullptr;
-        OrcTracerSettings c{};
-        uint32_t substeps = 0;
-        DevBuf<int> status;
-        int *raw = nullptr;               // pinned
-        hipEvent_t copied = nullptr;
-        bool pending = false;
-        TracerTracking() = default;
-        TracerTracking(const TracerTracking &) = delete;
-        TracerTracking &operator=(const TracerTracking &) = delete;
-        ~TracerTracking() { clear(); }
-        void clear() {
-            if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
-            if (raw) (void)hipHostFree(raw);
-            copied = nullptr; raw = nullptr;
-            status.release();
-            on = false; pending = false; set = nullptr; substeps = 0;
-        }
-    } tt;
+    // the post-processing arms (postproc_state.hpp): time statistics, probe history, group history, tracer tracking
+    TimeStats ts;
+    ProbeHistory ph;
+    GroupHistory gh;
+    TracerTracking tt;
 };
 
 int mesh_upload(OrcMesh &m, int64_t n_own, int64_t n_cells, int64_t n_faces, int32_t n_zones, const int64_t *face_c0, const int64_t *face_c1,
@@ -489,18 +395,6 @@ int wall_damping_validate(const OrcWallDamping &w);  // ORC_ERR_BAD_ARGUMENT wit
 // index if need be.
 int boundary_maps_dev(OrcMesh &m, const double *u, const double *v, const double *w, const double *p, double rho, double mu,
                       const double *mu_cell, uint32_t mask, double *out_dev, int *status_dev);
-// time statistics (time_stats.hip): what orc_solver_advance runs after scalar_step_dev — counts the step and, when the arm is on and the
-// step is due, takes one sample of weight dt; asynchronous on ctx().stream, nothing while the arm is off
-int stats_step_dev(SolverState &s);
-// probe history (probes.hip): what orc_solver_advance runs after stats_step_dev — counts the step and, when the history is on and the
-// step is due, samples one record on the device and starts its copy to the host; asynchronous on ctx().stream, nothing while it is off
-int probes_step_dev(SolverState &s);
-// tracer tracking (tracers.hip): what orc_solver_advance runs after probes_step_dev — while tracking is on, one launch that moves the
-// set through the step's velocity; asynchronous on ctx().stream, nothing while it is off
-int tracers_step_dev(SolverState &s);
-// group history (groups.hip): what orc_solver_advance runs last — counts the step and, when the history is on and the step is due,
-// reduces one record on the device and starts its copy to the host; asynchronous on ctx().stream, nothing while it is off
-int groups_step_dev(SolverState &s);
 // the Courant reduction (courant.hip): the largest convective rate of the current u, v, w over the owned cells (all ranks' on a
 // partitioned mesh) and the smallest ORC id that attains it (-1 on a partitioned mesh) to the host; rate_dev (may be null): the per-cell
 // values, internal order, n long, from the same launch.  Exchanges the fields' ghosts first; returns with the stream synchronised.

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -186,6 +187,33 @@ constexpr int clamp_partials_grid(int64_t g) { return g < 1 ? 1 : (g > (int64_t)
 
 inline int grid_for(int64_t work_items, int per_block = kBlock) {
     return clamp_partials_grid((work_items + per_block - 1) / per_block);
+}
+
+inline int popcount32(uint32_t m) { return __builtin_popcount(m); }
+
+// the caller's order out of a Morton-sorted set's (probes, tracers): dst[order[k]] = src[k]
+template <class T, class U>
+void unsort(const std::vector<int64_t> &order, const T *src, U *dst) {
+    for (size_t k = 0; k < order.size(); ++k) dst[order[k]] = (U)src[k];
+}
+
+// `reps` calls of launch() between two HIP events on the library stream, after one warm call: milliseconds per call.  `what` (may be
+// null): the text a bench entry reports when closing the measurement fails
+template <class Launch>
+int timed(int reps, Launch &&launch, float *ms, const char *what = nullptr) {
+    hipStream_t st = ctx().stream;
+    hipEvent_t e0, e1;
+    ORC_HIP(hipEventCreate(&e0));
+    ORC_HIP(hipEventCreate(&e1));
+    int rc = launch();  // warm
+    if (rc == ORC_OK && hipEventRecord(e0, st) != hipSuccess) rc = set_error(ORC_ERR_HIP, "hipEventRecord failed");
+    for (int i = 0; i < reps && rc == ORC_OK; ++i) rc = launch();
+    if (rc == ORC_OK && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess)) rc = set_error(ORC_ERR_HIP, "%s", what ? what : "hipEventRecord failed");
+    if (rc == ORC_OK && hipEventElapsedTime(ms, e0, e1) != hipSuccess) rc = set_error(ORC_ERR_HIP, "%s", what ? what : "hipEventElapsedTime failed");
+    if (rc == ORC_OK) *ms /= (float)std::max(reps, 1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
 }
 
 // ---------------- device helpers ----------------

@@ -115,7 +115,7 @@ int prepare(SolverState &s) {
         std::vector<int32_t> g(cell_order_ids(m).begin(), cell_order_ids(m).end());
         ORC_TRY(C.orc_id.upload(g.data(), g.size()));
     }
-    ORC_HIP(hipHostMalloc((void **)&C.raw, 2 * sizeof(double), hipHostMallocDefault));
+    ORC_TRY(C.raw.alloc(2));
     C.ready = true;
     return ORC_OK;
 }
@@ -147,14 +147,14 @@ int courant_dev(SolverState &s, double *rate_max, int64_t *cell, double *rate_de
     if (partitioned) { double *f[3] = {s.u.p, s.v.p, s.w.p}; ORC_TRY(m.halo.exchange(f, 3)); }
     ORC_TRY(launch(s, rate_dev));
     if (partitioned) ORC_TRY(comm_allreduce_max(C.out.p + 2, 2));  // exact: every rank gets the same bits and chooses the same next step
-    ORC_HIP(hipMemcpyAsync(C.raw, C.out.p + (partitioned ? 2 : 0), 2 * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
+    ORC_HIP(hipMemcpyAsync(C.raw.p, C.out.p + (partitioned ? 2 : 0), 2 * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
     ORC_HIP(hipStreamSynchronize(ctx().stream));
     if (partitioned) {
-        if (rate_max) *rate_max = C.raw[1] != 0. ? std::numeric_limits<double>::quiet_NaN() : C.raw[0];
+        if (rate_max) *rate_max = C.raw.p[1] != 0. ? std::numeric_limits<double>::quiet_NaN() : C.raw.p[0];
         if (cell) *cell = -1;  // no global tie rule is built
     } else {
-        if (rate_max) *rate_max = C.raw[0];
-        if (cell) *cell = m.n_own > 0 ? (int64_t)C.raw[1] : -1;
+        if (rate_max) *rate_max = C.raw.p[0];
+        if (cell) *cell = m.n_own > 0 ? (int64_t)C.raw.p[1] : -1;
     }
     return ORC_OK;
 }

@@ -702,12 +702,12 @@ OrcCut *orc_solver_cut_field(OrcSolver *s, uint32_t field_bit, double level, int
         return fail(set_error(ORC_ERR_BAD_ARGUMENT, "solver cut field: 0x%x is not exactly one OrcProbeField bit", field_bit));
     if (field_bit == (1u << ORC_PROBE_PHI) && !S.sc.on) return fail(set_error(ORC_ERR_BAD_ARGUMENT, "solver cut field: PHI needs the scalar arm (orc_solver_set_scalar)"));
     if (!std::isfinite(level)) return fail(set_error(ORC_ERR_BAD_ARGUMENT, "solver cut field: the level is not finite"));
-    const double *src[ORC_PROBE_N] = {S.u.p, S.v.p, S.w.p, S.p.p, S.sc.on ? S.sc.phi.p : nullptr, S.cell_viscosity()};
-    const double *phi = src[__builtin_ctz(field_bit)];
+    const SolverFields F = solver_field_table(S);
+    const double *phi = F.src[__builtin_ctz(field_bit)];
     DevBuf<double> constant;
     if (!phi) {  // MU while the viscosity arm is off: the constant, as the probes sample it
         if ((st = constant.alloc((size_t)S.mesh->n_cells)) != ORC_OK) return fail(st);
-        hipLaunchKernelGGL(fill_k, dim3(grid_for(S.mesh->n_cells)), dim3(kBlock), 0, ctx().stream, S.mesh->n_cells, S.mu, constant.p);
+        hipLaunchKernelGGL(fill_k, dim3(grid_for(S.mesh->n_cells)), dim3(kBlock), 0, ctx().stream, S.mesh->n_cells, F.mu, constant.p);
         phi = constant.p;
     }
     return cut_of_cell_field(S.mesh, phi, level, status);
@@ -762,25 +762,16 @@ int orc_solver_sample_cut(OrcSolver *s, const OrcCut *cut, uint32_t field_mask, 
     if (!cut) return set_error(ORC_ERR_BAD_ARGUMENT, "sample cut: null cut");
     SolverState &st = s->st;
     if (cut->mesh != st.mesh) return set_error(ORC_ERR_BAD_ARGUMENT, "sample cut: the cut was made in another mesh");
-    ORC_TRY(probes_validate_fields(st, field_mask, interpolation));
+    ORC_TRY(validate_fields(st, field_mask, interpolation));
     const bool linear = interpolation == ORC_PROBE_LINEAR;
     const int64_t n = linear ? cut->NP : cut->P;
     if (n < 1) return ORC_OK;
-    const int k = __builtin_popcount(field_mask);
-    DevBuf<double> off, dev;
-    DevBuf<int> status;
+    DevBuf<double> off;
     ORC_TRY(off.alloc(3 * (size_t)n));
-    ORC_TRY(dev.alloc((size_t)k * (size_t)n));
-    ORC_TRY(status.alloc(1));
-    ORC_TRY(status.zero());
     const int32_t *site = linear ? cut->owner.p : cut->cell.p;
     hipLaunchKernelGGL(cut_sites_k, dim3(grid_for(n)), dim3(kBlock), 0, ctx().stream, st.mesh->dev(), n, site, linear ? cut->points.p : (const double *)nullptr, off.p);
     ORC_HIP(hipGetLastError());
-    ORC_TRY(probes_launch_sample(st, site, off.p, n, field_mask, interpolation, dev.p, status.p));
-    ORC_TRY(dev.download(out, (size_t)k * (size_t)n));
-    int hs = 0;
-    ORC_TRY(status.download(&hs, 1));
-    return probes_sample_status(hs);
+    return sample_to_host(st, site, off.p, n, field_mask, interpolation, nullptr, out);  // synchronises: off is freed on return
 }
 
 int orc_cut_sample_cells(const OrcCut *cut, int32_t n_fields, const double *fields, double *out) {
@@ -833,9 +824,6 @@ int orc_bench_cut(OrcMesh *m, const double *cell_values, const double origin[3],
     ORC_TRY(C.poly_ptr.alloc((size_t)C.P + 1));
     ORC_TRY(C.cell.alloc((size_t)std::max<int64_t>(C.P, 1)));
     ORC_TRY(C.area.alloc((size_t)std::max<int64_t>(3 * C.P, 1)));
-    hipEvent_t e0, e1;
-    ORC_HIP(hipEventCreate(&e0));
-    ORC_HIP(hipEventCreate(&e1));
     int status = ORC_OK;
     for (int pass = 0; pass < 4 && status == ORC_OK; ++pass) {
         auto launch = [&]() -> int {
@@ -856,16 +844,10 @@ int orc_bench_cut(OrcMesh *m, const double *cell_values, const double origin[3],
             }
             }
         };
-        status = launch();  // warm-up
-        if (status == ORC_OK && hipEventRecord(e0, ctx().stream) != hipSuccess) status = set_error(ORC_ERR_HIP, "hipEventRecord failed");
-        for (int i = 0; i < reps && status == ORC_OK; ++i) status = launch();
         float ms = 0.f;
-        if (status == ORC_OK && (hipEventRecord(e1, ctx().stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-            status = set_error(ORC_ERR_HIP, "timing the cut passes failed");
-        avg_ms[pass] = (double)ms / reps;
+        status = timed(reps, launch, &ms, "timing the cut passes failed");
+        avg_ms[pass] = (double)ms;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     ORC_HIP(hipStreamSynchronize(ctx().stream));  // every buffer is freed on return
     return status;
 }

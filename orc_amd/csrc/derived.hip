@@ -139,8 +139,6 @@ __global__ __launch_bounds__(kBlock) void boundary_map_k(MeshDev M, BoundaryArgs
     }
 }
 
-int popcount32(uint32_t m) { return __builtin_popcount(m); }
-
 int fetch(DevBuf<int> &status, bool partitioned, const char *what) {
     int h = 0;
     ORC_TRY(status.download(&h, 1));
@@ -246,23 +244,16 @@ int orc_bench_derived_rate(OrcSolver *s, int reps, double *avg_ms) {
     DerivedArgs A{st.u.p, st.v.p, st.w.p, dev.p, 1u << ORC_DERIVED_CONVECTIVE_RATE};
     const int grid = grid_for(m.n_own);
     const bool lsq = st.settings.gradient_reconstruction == ORC_GRAD_LEAST_SQUARES;
-    auto launch = [&]() {
+    auto launch = [&] {
         if (lsq) hipLaunchKernelGGL(HIP_KERNEL_NAME(derived_cell_k<true>), dim3(grid), dim3(kBlock), 0, ctx().stream, m.dev(), A, status.p);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(derived_cell_k<false>), dim3(grid), dim3(kBlock), 0, ctx().stream, m.dev(), A, status.p);
+        return (int)ORC_OK;
     };
-    hipEvent_t e0, e1;
-    ORC_HIP(hipEventCreate(&e0));
-    ORC_HIP(hipEventCreate(&e1));
-    launch();  // warm-up
-    bool ok = hipEventRecord(e0, ctx().stream) == hipSuccess;
-    for (int i = 0; i < reps; ++i) launch();
     float ms = 0.f;
-    ok = ok && hipEventRecord(e1, ctx().stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    const bool ok = timed(reps, launch, &ms) == ORC_OK;
     ORC_HIP(hipStreamSynchronize(ctx().stream));  // dev is freed on return
     if (!ok || hipGetLastError() != hipSuccess) return set_error(ORC_ERR_HIP, "timing derived_cell_k failed");
-    *avg_ms = (double)ms / reps;
+    *avg_ms = (double)ms;
     return ORC_OK;
 }
 

@@ -297,12 +297,12 @@ int validate_groups(const OrcCellGroups *g, const OrcMesh *m) {
 
 // the solver's fields of `mask` (OrcProbeField bits, ascending) as the kernels take them
 int solver_fields(const SolverState &s, uint32_t mask, GroupField *f) {
-    const double *src[ORC_PROBE_N] = {s.u.p, s.v.p, s.w.p, s.p.p, s.sc.on ? s.sc.phi.p : nullptr, s.cell_viscosity()};
+    const SolverFields F = solver_field_table(s);
     int k = 0;
     for (int b = 0; b < ORC_PROBE_N; ++b) {
         if (!(mask >> b & 1)) continue;
-        f[k].x = src[b];
-        f[k].cval = b == ORC_PROBE_MU ? s.mu : 0.;
+        f[k].x = F.src[b];
+        f[k].cval = b == ORC_PROBE_MU ? F.mu : 0.;
         ++k;
     }
     return k;
@@ -310,20 +310,17 @@ int solver_fields(const SolverState &s, uint32_t mask, GroupField *f) {
 
 int validate_solver_report(const SolverState &s, const OrcCellGroups *g, uint32_t mask, int32_t weighting) {
     ORC_TRY(validate_groups(g, s.mesh));
-    ORC_TRY(probes_validate_fields(s, mask, ORC_PROBE_CELL));
+    ORC_TRY(validate_fields(s, mask, ORC_PROBE_CELL));
     return validate_weighting(weighting);
 }
 
-using GroupHistory = SolverState::GroupHistory;
-
-// the record on its way, if any, joins the history; its copy was started a step ago, so the wait is over before it begins
+// the record on its way, if any, joins the history as it is; its copy was started a step ago, so the wait is over before it begins
 int history_flush(SolverState &s) {
     GroupHistory &H = s.gh;
-    if (!H.pending) return ORC_OK;
-    ORC_HIP(hipEventSynchronize(H.copied));
-    H.pending = false;
-    const size_t len = record_len(*H.groups, H.n_fields);
-    H.values.insert(H.values.end(), H.raw, H.raw + len);
+    bool landed = false;
+    ORC_TRY(H.raw.wait(&landed));
+    if (!landed) return ORC_OK;
+    H.values.insert(H.values.end(), H.raw.host.p, H.raw.host.p + record_len(*H.groups, H.n_fields));
     H.times.push_back(H.pending_time);
     return ORC_OK;
 }
@@ -333,11 +330,9 @@ int history_enqueue(SolverState &s, double time) {
     GroupHistory &H = s.gh;
     GroupField f[ORC_PROBE_N];
     const int k = solver_fields(s, H.mask, f);
-    const size_t len = record_len(*H.groups, k);
     ORC_TRY(launch_report(*H.groups, f, k, H.weighting, H.rec.p));
-    ORC_HIP(hipMemcpyAsync(H.raw, H.rec.p, len * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
-    ORC_HIP(hipEventRecord(H.copied, ctx().stream));
-    H.pending = true;
+    ORC_TRY(H.raw.copy(0, H.rec.p, record_len(*H.groups, k) * sizeof(double)));
+    ORC_TRY(H.raw.mark());
     H.pending_time = time;
     return ORC_OK;
 }
@@ -347,17 +342,12 @@ int history_on(const SolverState &s) {
     return ORC_OK;
 }
 
-int popcount32(uint32_t m) { return __builtin_popcount(m); }
-
 }  // namespace
 
 int groups_step_dev(SolverState &s) {
-    GroupHistory &H = s.gh;
-    if (!H.on) return ORC_OK;
+    if (!s.gh.on) return ORC_OK;
     ORC_TRY(history_flush(s));  // the previous record: this step's iterations have synchronised the stream since
-    ++H.step;
-    if (H.step % H.interval != 0) return ORC_OK;
-    return history_enqueue(s, s.time);
+    return s.gh.due() ? history_enqueue(s, s.time) : ORC_OK;
 }
 
 }  // namespace orc
@@ -480,7 +470,7 @@ int orc_solver_group_statistics(OrcSolver *s, OrcCellGroups *g, uint32_t stat_fi
     ORC_TRY(ensure_init());
     if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
     SolverState &st = s->st;
-    const SolverState::TimeStats &T = st.ts;
+    const TimeStats &T = st.ts;
     ORC_TRY(validate_groups(g, st.mesh));
     if (!T.on) return set_error(ORC_ERR_BAD_ARGUMENT, "group statistics: the arm is off (orc_solver_set_time_statistics)");
     if (stat_field_mask == 0 || (stat_field_mask & ~T.field_mask))
@@ -512,36 +502,26 @@ int orc_solver_set_group_history(OrcSolver *s, OrcCellGroups *g, uint32_t field_
     }
     ORC_TRY(validate_solver_report(st, g, field_mask, weighting));
     if (interval == 0) return set_error(ORC_ERR_BAD_ARGUMENT, "group history: interval must be at least 1");
-    const int k = popcount32(field_mask);
+    GroupHistory H;
+    const int k = H.n_fields = popcount32(field_mask);
     const size_t len = record_len(*g, k);
-    DevBuf<double> rec;
-    ORC_TRY(rec.alloc(len));
+    ORC_TRY(H.rec.alloc(len));
     // one record of the current state first: its W (a property of the group set and the weighting) is what the read-out returns
     GroupField f[ORC_PROBE_N];
     (void)solver_fields(st, field_mask, f);
-    std::vector<double> first(len), w_of((size_t)g->n_groups);
-    ORC_TRY(launch_report(*g, f, k, weighting, rec.p));
-    ORC_TRY(rec.download(first.data(), len));
-    for (size_t q = 0; q < w_of.size(); ++q) w_of[q] = first[q * (size_t)(1 + kGroupRecord * k)];
-    double *raw = nullptr;
-    hipEvent_t ev = nullptr;
-    ORC_HIP(hipHostMalloc((void **)&raw, len * sizeof(double), hipHostMallocDefault));
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipHostFree(raw);
-        return set_error(ORC_ERR_HIP, "group history: hipEventCreate failed");
-    }
-    GroupHistory &H = st.gh;
-    H.clear();
-    H.rec = std::move(rec);
-    H.raw = raw;
-    H.copied = ev;
+    std::vector<double> first(len);
+    ORC_TRY(launch_report(*g, f, k, weighting, H.rec.p));
+    ORC_TRY(H.rec.download(first.data(), len));
+    H.w_of.resize((size_t)g->n_groups);
+    for (size_t q = 0; q < H.w_of.size(); ++q) H.w_of[q] = first[q * (size_t)(1 + kGroupRecord * k)];
+    ORC_TRY(H.raw.create(len, "group history"));
     H.groups = g;
     H.mask = field_mask;
     H.weighting = weighting;
-    H.n_fields = k;
     H.interval = interval;
-    H.w_of = std::move(w_of);
     H.on = true;
+    st.gh.clear();
+    st.gh = std::move(H);
     return ORC_OK;
 }
 
@@ -569,10 +549,7 @@ int orc_solver_group_history(OrcSolver *s, uint64_t first, uint64_t count, doubl
     ORC_TRY(history_on(st));
     ORC_TRY(history_flush(st));
     const GroupHistory &H = st.gh;
-    const uint64_t have = H.times.size();
-    if (first > have || count > have - first)
-        return set_error(ORC_ERR_BAD_ARGUMENT, "group history: records [%llu, %llu) asked for, %llu kept", (unsigned long long)first,
-                         (unsigned long long)(first + count), (unsigned long long)have);
+    ORC_TRY(history_range("group history", first, count, H.times.size()));
     const OrcCellGroups &g = *H.groups;
     const size_t len = record_len(g, H.n_fields), per = (size_t)g.n_groups * (size_t)H.n_fields;
     if (times) std::copy(H.times.begin() + (ptrdiff_t)first, H.times.begin() + (ptrdiff_t)(first + count), times);
@@ -596,23 +573,13 @@ int orc_bench_group_report(OrcSolver *s, OrcCellGroups *g, uint32_t field_mask, 
     if (k > kGroupFields) return set_error(ORC_ERR_BAD_ARGUMENT, "bench group report: at most %d fields (one batch)", kGroupFields);
     if (reps < 1) reps = 1;
     ORC_TRY(g->rec.ensure(record_len(*g, k)));
-    hipEvent_t e0, e1;
-    ORC_HIP(hipEventCreate(&e0));
-    ORC_HIP(hipEventCreate(&e1));
     int status = ORC_OK;
-    for (int pass = 0; pass < 2 && status == ORC_OK; ++pass) {
-        auto launch = [&] { return pass == 0 ? launch_chunks(*g, f, k, weighting) : launch_fold(*g, k, 0, k, g->rec.p); };
-        status = launch();  // warm-up (the fold's partials are the chunk pass's)
-        if (status == ORC_OK && hipEventRecord(e0, ctx().stream) != hipSuccess) status = set_error(ORC_ERR_HIP, "hipEventRecord failed");
-        for (int i = 0; i < reps && status == ORC_OK; ++i) status = launch();
+    for (int pass = 0; pass < 2 && status == ORC_OK; ++pass) {  // the warm call of the fold reads the chunk pass's partials
         float ms = 0.f;
-        if (status == ORC_OK && (hipEventRecord(e1, ctx().stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                                 hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-            status = set_error(ORC_ERR_HIP, "timing the group passes failed");
-        avg_ms[pass] = (double)ms / reps;
+        status = timed(reps, [&] { return pass == 0 ? launch_chunks(*g, f, k, weighting) : launch_fold(*g, k, 0, k, g->rec.p); }, &ms,
+                       "timing the group passes failed");
+        avg_ms[pass] = (double)ms;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     ORC_HIP(hipStreamSynchronize(ctx().stream));
     return status;
 }

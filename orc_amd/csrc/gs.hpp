@@ -70,22 +70,4 @@ int gsx_bicgstab1(const Coloring &C, const double *val, const double *b, double 
 
 __device__ __forceinline__ bool fin_nz(double v) { return v != 0. && isfinite(v); }
 
-// `reps` calls of launch() between two HIP events on the library stream, after one warm call: milliseconds per call
-template <class Launch>
-static int timed(int reps, Launch &&launch, float *ms) {
-    hipStream_t st = ctx().stream;
-    hipEvent_t e0, e1;
-    ORC_HIP(hipEventCreate(&e0));
-    ORC_HIP(hipEventCreate(&e1));
-    int rc = launch();  // warm
-    if (rc == ORC_OK && hipEventRecord(e0, st) != hipSuccess) rc = set_error(ORC_ERR_HIP, "hipEventRecord failed");
-    for (int i = 0; i < reps && rc == ORC_OK; ++i) rc = launch();
-    if (rc == ORC_OK && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess)) rc = set_error(ORC_ERR_HIP, "hipEventRecord failed");
-    if (rc == ORC_OK && hipEventElapsedTime(ms, e0, e1) != hipSuccess) rc = set_error(ORC_ERR_HIP, "hipEventElapsedTime failed");
-    if (rc == ORC_OK) *ms /= (float)std::max(reps, 1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
-}
-
 }  // namespace orc

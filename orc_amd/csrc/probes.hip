@@ -254,8 +254,6 @@ __global__ __launch_bounds__(kBlock) void probe_sample_k(MeshDev M, SampleArgs A
 }
 
 // ====================================================================== host side
-int popcount32(uint32_t m) { return __builtin_popcount(m); }
-
 // the mesh's spheres and its internal -> ORC map, built once
 int ensure_tiles(OrcMesh &m) {
     if (m.probe_tiles) return ORC_OK;
@@ -358,6 +356,8 @@ void morton_order(int64_t n, const double *xyz, std::vector<int64_t> &order) {
     std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return key[(size_t)a] < key[(size_t)b]; });
 }
 
+}  // namespace
+
 OrcProbes *locate(OrcMesh *m, int64_t n, const double *xyz, bool cull, int forced_slabs, int *status) {
     auto fail = [&](int st) { if (status) *status = st; return (OrcProbes *)nullptr; };
     if (status) *status = ORC_OK;
@@ -401,20 +401,7 @@ OrcProbes *locate(OrcMesh *m, int64_t n, const double *xyz, bool cull, int force
     return P.release();
 }
 
-// the caller's order out of the search's: dst[order[k]] = src[k]
-template <class T, class U>
-void unsort(const std::vector<int64_t> &order, const T *src, U *dst) {
-    for (size_t k = 0; k < order.size(); ++k) dst[order[k]] = (U)src[k];
-}
-
 // ------------------------------------------------------------------ sampling
-int validate_fields(const SolverState &s, uint32_t mask, int32_t interpolation);
-int validate_sample(const SolverState &s, const OrcProbes *p, uint32_t mask, int32_t interpolation) {
-    if (!p) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: null probe set");
-    if (p->mesh != s.mesh) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: the probe set was located in another mesh");
-    return validate_fields(s, mask, interpolation);
-}
-
 int validate_fields(const SolverState &s, uint32_t mask, int32_t interpolation) {
     if (mask == 0 || (mask & ~kAllFields)) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: mask 0x%x selects nothing or an unknown field", mask);
     if ((mask & (1u << ORC_PROBE_PHI)) && !s.sc.on) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: PHI needs the scalar arm (orc_solver_set_scalar)");
@@ -425,12 +412,11 @@ int validate_fields(const SolverState &s, uint32_t mask, int32_t interpolation) 
     return ORC_OK;
 }
 
-// the fields of `mask` at n points given by cell and offset [3][n] into out_dev [popcount][n] (the set's device order), asynchronous on
-// ctx().stream
 int launch_sample(const SolverState &s, const int32_t *cell, const double *off, int64_t n, uint32_t mask, int32_t interpolation, double *out_dev,
                   int *status_dev) {
-    SampleArgs A{s.u.p, s.v.p, s.w.p, s.p.p, (mask & (1u << ORC_PROBE_PHI)) ? s.sc.phi.p : nullptr, s.cell_viscosity(), s.mu,
-                 cell, off, n, out_dev, mask, interpolation == ORC_PROBE_LINEAR ? 1 : 0, s.settings.q1_compat};
+    const SolverFields F = solver_field_table(s);
+    SampleArgs A{F.src[ORC_PROBE_U], F.src[ORC_PROBE_V], F.src[ORC_PROBE_W], F.src[ORC_PROBE_P], (mask & (1u << ORC_PROBE_PHI)) ? F.src[ORC_PROBE_PHI] : nullptr,
+                 F.src[ORC_PROBE_MU], F.mu, cell, off, n, out_dev, mask, interpolation == ORC_PROBE_LINEAR ? 1 : 0, s.settings.q1_compat};
     if (s.settings.gradient_reconstruction == ORC_GRAD_LEAST_SQUARES)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(probe_sample_k<true>), dim3(grid_for(n)), dim3(kBlock), 0, ctx().stream, s.mesh->dev(), A, status_dev);
     else
@@ -445,58 +431,72 @@ int sample_status(int h) {
     return ORC_OK;
 }
 
-// one record [n_fields][n] in the set's device order to the end of the history, in the caller's point order
-void append_record(SolverState::ProbeHistory &H, double time, const double *rec) {
-    const size_t n = (size_t)H.probes->n, base = H.values.size();
-    H.values.resize(base + (size_t)H.n_fields * n);
-    for (int k = 0; k < H.n_fields; ++k) unsort(H.probes->order, rec + (size_t)k * n, H.values.data() + base + (size_t)k * n);
-    H.times.push_back(time);
-}
-
-// the record on its way, if any, joins the history; its copy was started a step ago, so the wait is over before it begins
-int history_flush(SolverState &s) {
-    SolverState::ProbeHistory &H = s.ph;
-    if (!H.pending) return ORC_OK;
-    ORC_HIP(hipEventSynchronize(H.copied));
-    H.pending = false;
-    const size_t len = (size_t)H.n_fields * (size_t)H.probes->n;
-    int h = 0;
-    std::memcpy(&h, H.raw + len, sizeof(int));
-    ORC_TRY(sample_status(h));
-    append_record(H, H.pending_time, H.raw);
+int sample_to_host(const SolverState &s, const int32_t *cell, const double *off, int64_t n, uint32_t mask, int32_t interpolation,
+                   const std::vector<int64_t> *order, double *out, DevBuf<int> *keep_status) {
+    const size_t len = (size_t)popcount32(mask) * (size_t)n;
+    DevBuf<double> dev;
+    DevBuf<int> own, &status = keep_status ? *keep_status : own;
+    ORC_TRY(dev.alloc(len));
+    ORC_TRY(status.alloc(1));
+    ORC_TRY(status.zero());
+    ORC_TRY(launch_sample(s, cell, off, n, mask, interpolation, dev.p, status.p));
+    std::vector<double> h(out && order ? len : 0);
+    if (out) ORC_TRY(dev.download(order ? h.data() : out, len));
+    int hs = 0;
+    ORC_TRY(status.download(&hs, 1));
+    ORC_TRY(sample_status(hs));
+    for (size_t q = 0; out && order && q < len; q += (size_t)n) unsort(*order, h.data() + q, out + q);
     return ORC_OK;
 }
 
-// one record of the current state, sampled and sent on its way
+namespace {
+
+int validate_sample(const SolverState &s, const OrcProbes *p, uint32_t mask, int32_t interpolation) {
+    if (!p) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: null probe set");
+    if (p->mesh != s.mesh) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: the probe set was located in another mesh");
+    return validate_fields(s, mask, interpolation);
+}
+
+int history_on(const SolverState &s) {
+    if (!s.ph.on) return set_error(ORC_ERR_BAD_ARGUMENT, "probe history: the history is off (orc_solver_set_probe_history)");
+    return ORC_OK;
+}
+
+// the record on its way, if any, joins the history in the caller's point order; its copy was started a step ago, so the wait is over
+// before it begins
+int history_flush(SolverState &s) {
+    ProbeHistory &H = s.ph;
+    bool landed = false;
+    ORC_TRY(H.raw.wait(&landed));
+    if (!landed) return ORC_OK;
+    const size_t n = (size_t)H.probes->n, len = (size_t)H.n_fields * n, base = H.values.size();
+    int h = 0;
+    std::memcpy(&h, H.raw.host.p + len, sizeof(int));
+    ORC_TRY(sample_status(h));
+    H.values.resize(base + len);
+    for (size_t q = 0; q < len; q += n) unsort(H.probes->order, H.raw.host.p + q, H.values.data() + base + q);
+    H.times.push_back(H.pending_time);
+    return ORC_OK;
+}
+
+// one record of the current state, sampled and sent on its way: the record and the status word are two copies
 int history_enqueue(SolverState &s, double time) {
-    SolverState::ProbeHistory &H = s.ph;
+    ProbeHistory &H = s.ph;
     const size_t len = (size_t)H.n_fields * (size_t)H.probes->n;
     ORC_TRY(launch_sample(s, H.probes->cell.p, H.probes->off.p, H.probes->n, H.mask, H.interpolation, H.rec.p, H.status.p));
-    ORC_HIP(hipMemcpyAsync(H.raw, H.rec.p, len * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
-    ORC_HIP(hipMemcpyAsync(H.raw + len, H.status.p, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-    ORC_HIP(hipEventRecord(H.copied, ctx().stream));
-    H.pending = true;
+    ORC_TRY(H.raw.copy(0, H.rec.p, len * sizeof(double)));
+    ORC_TRY(H.raw.copy(len, H.status.p, sizeof(int)));
+    ORC_TRY(H.raw.mark());
     H.pending_time = time;
     return ORC_OK;
 }
 
 }  // namespace
 
-OrcProbes *probes_locate(OrcMesh *m, int64_t n, const double *xyz, int *status) { return locate(m, n, xyz, true, 0, status); }
-int probes_launch_sample(const SolverState &s, const int32_t *cell, const double *off, int64_t n, uint32_t mask, int32_t interpolation,
-                         double *out_dev, int *status_dev) {
-    return launch_sample(s, cell, off, n, mask, interpolation, out_dev, status_dev);
-}
-int probes_validate_fields(const SolverState &s, uint32_t mask, int32_t interpolation) { return validate_fields(s, mask, interpolation); }
-int probes_sample_status(int h) { return sample_status(h); }
-
 int probes_step_dev(SolverState &s) {
-    SolverState::ProbeHistory &H = s.ph;
-    if (!H.on) return ORC_OK;
+    if (!s.ph.on) return ORC_OK;
     ORC_TRY(history_flush(s));  // the previous record: this step's iterations have synchronised the stream since
-    ++H.step;
-    if (H.step % H.interval != 0) return ORC_OK;
-    return history_enqueue(s, s.time);
+    return s.ph.due() ? history_enqueue(s, s.time) : ORC_OK;
 }
 
 }  // namespace orc
@@ -547,21 +547,7 @@ int orc_solver_sample_probes(OrcSolver *s, const OrcProbes *p, uint32_t field_ma
     if (!s || !out) return set_error(ORC_ERR_BAD_ARGUMENT, "probes: null argument");
     SolverState &st = s->st;
     ORC_TRY(validate_sample(st, p, field_mask, interpolation));
-    const int k = popcount32(field_mask);
-    const size_t n = (size_t)p->n;
-    DevBuf<double> dev;
-    DevBuf<int> status;
-    ORC_TRY(dev.alloc((size_t)k * n));
-    ORC_TRY(status.alloc(1));
-    ORC_TRY(status.zero());
-    ORC_TRY(launch_sample(st, p->cell.p, p->off.p, p->n, field_mask, interpolation, dev.p, status.p));
-    std::vector<double> h((size_t)k * n);
-    ORC_TRY(dev.download(h.data(), h.size()));
-    int hs = 0;
-    ORC_TRY(status.download(&hs, 1));
-    ORC_TRY(sample_status(hs));
-    for (int q = 0; q < k; ++q) unsort(p->order, h.data() + (size_t)q * n, out + (size_t)q * n);
-    return ORC_OK;
+    return sample_to_host(st, p->cell.p, p->off.p, p->n, field_mask, interpolation, &p->order, out);
 }
 
 int orc_solver_set_probe_history(OrcSolver *s, const OrcProbes *p, uint32_t field_mask, int32_t interpolation, uint64_t interval) {
@@ -575,36 +561,19 @@ int orc_solver_set_probe_history(OrcSolver *s, const OrcProbes *p, uint32_t fiel
     ORC_TRY(validate_sample(st, p, field_mask, interpolation));
     if (interval == 0) return set_error(ORC_ERR_BAD_ARGUMENT, "probe history: interval must be at least 1");
     // one record of the current state first: a zone type the assembly refuses or a singular system is refused here, nothing changed
-    const int k = popcount32(field_mask);
-    const size_t len = (size_t)k * (size_t)p->n;
-    DevBuf<double> rec;
-    DevBuf<int> status;
-    ORC_TRY(rec.alloc(len));
-    ORC_TRY(status.alloc(1));
-    ORC_TRY(status.zero());
-    ORC_TRY(launch_sample(st, p->cell.p, p->off.p, p->n, field_mask, interpolation, rec.p, status.p));
-    int hs = 0;
-    ORC_TRY(status.download(&hs, 1));
-    ORC_TRY(sample_status(hs));
-    double *raw = nullptr;
-    hipEvent_t ev = nullptr;
-    ORC_HIP(hipHostMalloc((void **)&raw, (len + 1) * sizeof(double), hipHostMallocDefault));
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipHostFree(raw);
-        return set_error(ORC_ERR_HIP, "probe history: hipEventCreate failed");
-    }
-    SolverState::ProbeHistory &H = st.ph;
-    H.clear();
-    H.rec = std::move(rec);
-    H.status = std::move(status);
-    H.raw = raw;
-    H.copied = ev;
+    ProbeHistory H;
+    ORC_TRY(sample_to_host(st, p->cell.p, p->off.p, p->n, field_mask, interpolation, nullptr, nullptr, &H.status));
+    H.n_fields = popcount32(field_mask);
+    const size_t len = (size_t)H.n_fields * (size_t)p->n;
+    ORC_TRY(H.rec.alloc(len));
+    ORC_TRY(H.raw.create(len + 1, "probe history"));
     H.probes = p;
     H.mask = field_mask;
     H.interpolation = interpolation;
-    H.n_fields = k;
     H.interval = interval;
     H.on = true;
+    st.ph.clear();
+    st.ph = std::move(H);
     return ORC_OK;
 }
 
@@ -612,7 +581,7 @@ int orc_solver_record_probes(OrcSolver *s, double tag) {
     ORC_TRY(ensure_init());
     if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
     SolverState &st = s->st;
-    if (!st.ph.on) return set_error(ORC_ERR_BAD_ARGUMENT, "probe history: the history is off (orc_solver_set_probe_history)");
+    ORC_TRY(history_on(st));
     ORC_TRY(history_flush(st));
     ORC_TRY(history_enqueue(st, tag));
     return history_flush(st);
@@ -621,8 +590,7 @@ int orc_solver_record_probes(OrcSolver *s, double tag) {
 int64_t orc_solver_probe_history_count(OrcSolver *s) {
     if (ensure_init() != ORC_OK) return -1;
     if (!s) { (void)set_error(ORC_ERR_BAD_ARGUMENT, "null solver"); return -1; }
-    if (!s->st.ph.on) { (void)set_error(ORC_ERR_BAD_ARGUMENT, "probe history: the history is off (orc_solver_set_probe_history)"); return -1; }
-    if (history_flush(s->st) != ORC_OK) return -1;
+    if (history_on(s->st) != ORC_OK || history_flush(s->st) != ORC_OK) return -1;
     return (int64_t)s->st.ph.times.size();
 }
 
@@ -630,13 +598,10 @@ int orc_solver_probe_history(OrcSolver *s, uint64_t first, uint64_t count, doubl
     ORC_TRY(ensure_init());
     if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
     SolverState &st = s->st;
-    if (!st.ph.on) return set_error(ORC_ERR_BAD_ARGUMENT, "probe history: the history is off (orc_solver_set_probe_history)");
+    ORC_TRY(history_on(st));
     ORC_TRY(history_flush(st));
-    const SolverState::ProbeHistory &H = st.ph;
-    const uint64_t have = H.times.size();
-    if (first > have || count > have - first)
-        return set_error(ORC_ERR_BAD_ARGUMENT, "probe history: records [%llu, %llu) asked for, %llu kept", (unsigned long long)first,
-                         (unsigned long long)(first + count), (unsigned long long)have);
+    const ProbeHistory &H = st.ph;
+    ORC_TRY(history_range("probe history", first, count, H.times.size()));
     const size_t len = (size_t)H.n_fields * (size_t)H.probes->n;
     if (times) std::copy(H.times.begin() + (ptrdiff_t)first, H.times.begin() + (ptrdiff_t)(first + count), times);
     if (out) std::copy(H.values.begin() + (ptrdiff_t)(first * len), H.values.begin() + (ptrdiff_t)((first + count) * len), out);
@@ -661,23 +626,13 @@ int orc_bench_probe_locate(OrcMesh *m, const OrcProbes *p, int cull, int reps, d
     OrcProbes scratch;
     ORC_TRY(alloc_scratch(p->n, slabs, S));
     ORC_TRY(alloc_results(p->n, scratch));
-    hipEvent_t e0, e1;
-    ORC_HIP(hipEventCreate(&e0));
-    ORC_HIP(hipEventCreate(&e1));
     int status = ORC_OK;
-    for (int pass = 0; pass < 2 && status == ORC_OK; ++pass) {
-        auto launch = [&] { return pass == 0 ? launch_search(*m, *p, cull != 0, slabs, S) : launch_walk(*m, *p, scratch, S); };
-        status = launch();  // warm-up (the walk's start cells are the search's)
-        if (status == ORC_OK && hipEventRecord(e0, ctx().stream) != hipSuccess) status = set_error(ORC_ERR_HIP, "hipEventRecord failed");
-        for (int i = 0; i < reps && status == ORC_OK; ++i) status = launch();
+    for (int pass = 0; pass < 2 && status == ORC_OK; ++pass) {  // the warm call of the walk starts from the search's cells
         float ms = 0.f;
-        if (status == ORC_OK && (hipEventRecord(e1, ctx().stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                                 hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-            status = set_error(ORC_ERR_HIP, "timing the probe passes failed");
-        avg_ms[pass] = (double)ms / reps;
+        status = timed(reps, [&] { return pass == 0 ? launch_search(*m, *p, cull != 0, slabs, S) : launch_walk(*m, *p, scratch, S); }, &ms,
+                       "timing the probe passes failed");
+        avg_ms[pass] = (double)ms;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     unsigned long long c[2] = {0, 0};
     ORC_TRY(S.counters.download(c, 2));  // synchronises: the scratch is freed on return
     ORC_TRY(status);

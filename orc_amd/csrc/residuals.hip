@@ -140,13 +140,12 @@ int monitors_enable(SolverState &s, bool on) {
         ORC_TRY(M.partials.ensure((size_t)(3 * kResKinds + 3) * kMaxPartials));
         ORC_TRY(M.dev.ensure((size_t)(SolverState::Monitor::kSums + SolverState::Monitor::kMaxima)));
         ORC_TRY(M.dev.zero());
-        if (!M.raw) ORC_HIP(hipHostMalloc((void **)&M.raw, sizeof(double) * (SolverState::Monitor::kSums + SolverState::Monitor::kMaxima), hipHostMallocDefault));
+        if (!M.raw.p) ORC_TRY(M.raw.alloc((size_t)(SolverState::Monitor::kSums + SolverState::Monitor::kMaxima)));
     } else {
         ORC_HIP(hipStreamSynchronize(ctx().stream));  // no pass of the monitor is in flight when its buffers go
         M.partials.release();
         M.dev.release();
-        if (M.raw) (void)hipHostFree(M.raw);
-        M.raw = nullptr;
+        M.raw.release();
     }
     M.history.clear();
     M.seen = 0;
@@ -198,18 +197,18 @@ int monitor_fetch(SolverState &s) {
         ORC_TRY(comm_allreduce_sum(M.dev.p, kS));
         ORC_TRY(comm_allreduce_max(M.dev.p + kS, kM));
     }
-    ORC_HIP(hipMemcpyAsync(M.raw, M.dev.p, sizeof(double) * (kS + kM), hipMemcpyDeviceToHost, ctx().stream));
+    ORC_HIP(hipMemcpyAsync(M.raw.p, M.dev.p, sizeof(double) * (kS + kM), hipMemcpyDeviceToHost, ctx().stream));
     return ORC_OK;
 }
 
 void monitor_append(SolverState &s) {
     SolverState::Monitor &M = s.mon;
     double rec[ORC_RESIDUAL_N] = {0.};
-    for (int k = 0; k < 9; ++k) rec[ORC_RESIDUAL_MOMENTUM_L1 + k] = M.raw[kDevMomentumSums + k];
-    for (int k = 0; k < 3; ++k) rec[ORC_RESIDUAL_MOMENTUM_MAX + k] = M.raw[kDevMomentumMax + k];
-    rec[ORC_RESIDUAL_CONTINUITY_L1] = M.raw[kDevContinuitySums];
-    rec[ORC_RESIDUAL_CONTINUITY_SQ] = M.raw[kDevContinuitySums + 1];
-    rec[ORC_RESIDUAL_CONTINUITY_MAX] = M.raw[kDevContinuityMax];
+    for (int k = 0; k < 9; ++k) rec[ORC_RESIDUAL_MOMENTUM_L1 + k] = M.raw.p[kDevMomentumSums + k];
+    for (int k = 0; k < 3; ++k) rec[ORC_RESIDUAL_MOMENTUM_MAX + k] = M.raw.p[kDevMomentumMax + k];
+    rec[ORC_RESIDUAL_CONTINUITY_L1] = M.raw.p[kDevContinuitySums];
+    rec[ORC_RESIDUAL_CONTINUITY_SQ] = M.raw.p[kDevContinuitySums + 1];
+    rec[ORC_RESIDUAL_CONTINUITY_MAX] = M.raw.p[kDevContinuityMax];
     residual_record_finish(rec, M.seen, &M.scale);
     M.seen += 1;
     M.history.insert(M.history.end(), rec, rec + ORC_RESIDUAL_N);

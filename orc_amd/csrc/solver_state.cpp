@@ -207,7 +207,6 @@ SolverState::~SolverState() {
     }
     destroy_side(side);
     if (prep_stream) stream_destroy(prep_stream);
-    if (mon.raw) (void)hipHostFree(mon.raw);
 }
 
 }  // namespace orc

@@ -20,7 +20,6 @@ namespace orc {
 
 namespace {
 
-using TimeStats = SolverState::TimeStats;
 
 constexpr uint32_t kMeanFields = 0xFu, kStressFields = 0x7F0u, kMuFields = 1u << ORC_STAT_MU, kPhiFields = 0x1F000u;
 constexpr uint32_t kAllGroups = ORC_STAT_GROUP_MEAN | ORC_STAT_GROUP_STRESS | ORC_STAT_GROUP_VISCOSITY | ORC_STAT_GROUP_SCALAR | ORC_STAT_GROUP_BOUNDARY;
@@ -168,8 +167,6 @@ int validate(const SolverState &s, const OrcTimeStatistics &c) {
     return ORC_OK;
 }
 
-int popcount32(uint32_t m) { return __builtin_popcount(m); }
-
 }  // namespace
 
 int stats_step_dev(SolverState &s) {
@@ -204,11 +201,11 @@ int orc_solver_set_time_statistics(OrcSolver *s, const OrcTimeStatistics *c) {
     SolverState &st = s->st;
     if (!c) {  // off: advance launches nothing of the arm from here on
         ORC_HIP(hipStreamSynchronize(ctx().stream));
-        st.ts = SolverState::TimeStats();
+        st.ts = TimeStats();
         return ORC_OK;
     }
     ORC_TRY(validate(st, *c));
-    SolverState::TimeStats fresh;
+    TimeStats fresh;
     fresh.c = *c;
     fresh.field_mask = fields_of(c->groups);
     fresh.n_fields = popcount32(fresh.field_mask);
@@ -247,7 +244,7 @@ int orc_solver_sample_statistics(OrcSolver *s, double weight) {
 int orc_solver_reset_statistics(OrcSolver *s) {
     ORC_TRY(ensure_init());
     if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
-    SolverState::TimeStats &T = s->st.ts;
+    TimeStats &T = s->st.ts;
     if (!T.on) return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: the arm is off (orc_solver_set_time_statistics)");
     ORC_TRY(T.acc.zero());
     ORC_TRY(T.bnd.zero());
@@ -259,7 +256,7 @@ int orc_solver_reset_statistics(OrcSolver *s) {
 int orc_solver_statistics_info(OrcSolver *s, uint64_t *samples, double *weight_sum, int32_t *n_fields, int64_t *n_boundary_faces) {
     ORC_TRY(ensure_init());
     if (!s) return set_error(ORC_ERR_BAD_ARGUMENT, "null solver");
-    const SolverState::TimeStats &T = s->st.ts;
+    const TimeStats &T = s->st.ts;
     if (!T.on) return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: the arm is off (orc_solver_set_time_statistics)");
     if (samples) *samples = T.samples;
     if (weight_sum) *weight_sum = T.W;
@@ -272,7 +269,7 @@ int orc_solver_get_statistics(OrcSolver *s, uint32_t field_mask, int32_t form, d
     ORC_TRY(ensure_init());
     if (!s || !out) return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: null argument");
     SolverState &st = s->st;
-    const SolverState::TimeStats &T = st.ts;
+    const TimeStats &T = st.ts;
     if (!T.on) return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: the arm is off (orc_solver_set_time_statistics)");
     if (field_mask == 0 || (field_mask & ~T.field_mask))
         return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: mask 0x%x selects nothing, an unknown field or a field whose group is off", field_mask);
@@ -298,7 +295,7 @@ int orc_solver_set_statistics_state(OrcSolver *s, uint64_t samples, double weigh
     ORC_TRY(ensure_init());
     if (!s || !raw) return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: null argument");
     SolverState &st = s->st;
-    SolverState::TimeStats &T = st.ts;
+    TimeStats &T = st.ts;
     if (!T.on) return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: the arm is off (orc_solver_set_time_statistics)");
     if (field_mask != T.field_mask)
         return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: a state holds exactly the enabled fields (mask 0x%x, got 0x%x)", T.field_mask, field_mask);
@@ -322,7 +319,7 @@ int orc_solver_get_boundary_statistics(OrcSolver *s, double *out) {
     ORC_TRY(ensure_init());
     if (!s || !out) return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: null argument");
     SolverState &st = s->st;
-    const SolverState::TimeStats &T = st.ts;
+    const TimeStats &T = st.ts;
     if (!T.on || !(T.c.groups & ORC_STAT_GROUP_BOUNDARY))
         return set_error(ORC_ERR_BAD_ARGUMENT, "time statistics: the BOUNDARY group is off (orc_solver_set_time_statistics)");
     if (T.nb > 0) ORC_TRY(T.bnd.download(out, (size_t)ORC_STAT_BOUNDARY_N * (size_t)T.nb));
@@ -333,7 +330,7 @@ int orc_bench_time_statistics(OrcSolver *s, int reps, double avg_ms[2]) {
     ORC_TRY(ensure_init());
     if (!s || !avg_ms) return set_error(ORC_ERR_BAD_ARGUMENT, "null argument");
     SolverState &st = s->st;
-    SolverState::TimeStats &T = st.ts;
+    TimeStats &T = st.ts;
     if (!T.on) return set_error(ORC_ERR_BAD_ARGUMENT, "bench time statistics: the arm is off (orc_solver_set_time_statistics)");
     if (reps < 1) reps = 1;
     const bool boundary = (T.c.groups & ORC_STAT_GROUP_BOUNDARY) && T.nb > 0;
@@ -344,25 +341,15 @@ int orc_bench_time_statistics(OrcSolver *s, int reps, double avg_ms[2]) {
         ORC_TRY(mean.alloc((size_t)ORC_STAT_BOUNDARY_N * (size_t)T.nb));
         ORC_TRY(mean.zero());
     }
-    hipEvent_t e0, e1;
-    ORC_HIP(hipEventCreate(&e0));
-    ORC_HIP(hipEventCreate(&e1));
     int status = ORC_OK;
     for (int pass = 0; pass < 2 && status == ORC_OK; ++pass) {
         avg_ms[pass] = 0.;
         if (pass == 1 && !boundary) break;
-        auto launch = [&] { return pass == 0 ? k_time_stats(st, acc.p, 1., 0.5) : k_boundary_stats(st, T.bnd_now.p, mean.p, 0.5); };
-        status = launch();  // warm-up
-        if (status == ORC_OK && hipEventRecord(e0, ctx().stream) != hipSuccess) status = set_error(ORC_ERR_HIP, "hipEventRecord failed");
-        for (int i = 0; i < reps && status == ORC_OK; ++i) status = launch();
         float ms = 0.f;
-        if (status == ORC_OK && (hipEventRecord(e1, ctx().stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                                 hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-            status = set_error(ORC_ERR_HIP, "timing the statistics passes failed");
-        avg_ms[pass] = (double)ms / reps;
+        status = timed(reps, [&] { return pass == 0 ? k_time_stats(st, acc.p, 1., 0.5) : k_boundary_stats(st, T.bnd_now.p, mean.p, 0.5); }, &ms,
+                       "timing the statistics passes failed");
+        avg_ms[pass] = (double)ms;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     ORC_HIP(hipStreamSynchronize(ctx().stream));  // the scratch is freed on return
     return status;
 }

@@ -186,23 +186,16 @@ int launch_advect(const SolverState &s, const OrcTracerSettings &c, double hs, c
     return ORC_OK;
 }
 
-// the caller's order out of the set's: dst[order[k]] = src[k]
-template <class T, class U>
-void unsort(const std::vector<int64_t> &order, const T *src, U *dst) {
-    for (size_t k = 0; k < order.size(); ++k) dst[order[k]] = (U)src[k];
-}
-
 // the status word of a tracking step on its way, if any
 int tracking_flush(SolverState &s) {
-    SolverState::TracerTracking &T = s.tt;
-    if (!T.pending) return ORC_OK;
-    ORC_HIP(hipEventSynchronize(T.copied));
-    T.pending = false;
-    const int h = *T.raw;
+    TracerTracking &T = s.tt;
+    bool landed = false;
+    ORC_TRY(T.raw.wait(&landed));
+    const int h = landed ? *T.raw.host.p : ORC_OK;
     if (h != ORC_OK) {
-        *T.raw = 0;
+        *T.raw.host.p = 0;
         ORC_TRY(T.status.zero());
-        return probes_sample_status(h);
+        return sample_status(h);
     }
     return ORC_OK;
 }
@@ -210,16 +203,14 @@ int tracking_flush(SolverState &s) {
 }  // namespace
 
 int tracers_step_dev(SolverState &s) {
-    SolverState::TracerTracking &T = s.tt;
+    TracerTracking &T = s.tt;
     if (!T.on) return ORC_OK;
     ORC_TRY(tracking_flush(s));  // the previous step's word: this step's iterations have synchronised the stream since
     OrcTracers &t = *T.set;
     ORC_TRY(launch_advect(s, T.c, s.dt / (double)T.substeps, view(t.st[t.cur]), view(t.st[1 - t.cur]), t.n, T.substeps, nullptr, nullptr, T.status.p));
     t.cur = 1 - t.cur;  // every reader of the set is ordered behind the launch on the stream
-    ORC_HIP(hipMemcpyAsync(T.raw, T.status.p, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-    ORC_HIP(hipEventRecord(T.copied, ctx().stream));
-    T.pending = true;
-    return ORC_OK;
+    ORC_TRY(T.raw.copy(0, T.status.p, sizeof(int)));
+    return T.raw.mark();
 }
 
 }  // namespace orc
@@ -239,7 +230,7 @@ void orc_tracer_settings_default(OrcTracerSettings *c) {
 }
 
 OrcTracers *orc_tracers_create(OrcMesh *m, int64_t n, const double *xyz, int *status) {
-    std::unique_ptr<OrcProbes> P(probes_locate(m, n, xyz, status));  // the device, the arguments and the mesh are looked at there
+    std::unique_ptr<OrcProbes> P(locate(m, n, xyz, true, 0, status));  // the device, the arguments and the mesh are looked at there
     if (!P) return nullptr;
     auto fail = [&](int st) { if (status) *status = st; (void)hipStreamSynchronize(ctx().stream); return (OrcTracers *)nullptr; };
     std::unique_ptr<OrcTracers> t(new OrcTracers());
@@ -341,7 +332,7 @@ int orc_solver_advect_tracers(OrcSolver *s, OrcTracers *t, const OrcTracerSettin
             return launched;
         }
         ORC_TRY(status.download(&hs, 1));  // the one synchronisation
-        ORC_TRY(probes_sample_status(hs));  // refused: the set is still its first buffer
+        ORC_TRY(sample_status(hs));  // refused: the set is still its first buffer
         t->cur = 1 - t->cur;
     }
     if (record_stride > 0) {
@@ -365,23 +356,9 @@ int orc_solver_sample_tracers(OrcSolver *s, const OrcTracers *t, uint32_t field_
     if (!s || !t || !out) return set_error(ORC_ERR_BAD_ARGUMENT, "tracers: null argument");
     SolverState &st = s->st;
     if (t->mesh != st.mesh) return set_error(ORC_ERR_BAD_ARGUMENT, "tracers: the set was seeded in another mesh");
-    ORC_TRY(probes_validate_fields(st, field_mask, interpolation));
-    const int k = __builtin_popcount(field_mask);
-    const size_t n = (size_t)t->n;
-    DevBuf<double> dev;
-    DevBuf<int> status;
-    ORC_TRY(dev.alloc((size_t)k * n));
-    ORC_TRY(status.alloc(1));
-    ORC_TRY(status.zero());
+    ORC_TRY(validate_fields(st, field_mask, interpolation));
     const TracerState &A = t->st[t->cur];
-    ORC_TRY(probes_launch_sample(st, A.cell.p, A.off.p, t->n, field_mask, interpolation, dev.p, status.p));
-    std::vector<double> h((size_t)k * n);
-    ORC_TRY(dev.download(h.data(), h.size()));
-    int hs = 0;
-    ORC_TRY(status.download(&hs, 1));
-    ORC_TRY(probes_sample_status(hs));
-    for (int q = 0; q < k; ++q) unsort(t->order, h.data() + (size_t)q * n, out + (size_t)q * n);
-    return ORC_OK;
+    return sample_to_host(st, A.cell.p, A.off.p, t->n, field_mask, interpolation, &t->order, out);
 }
 
 int orc_solver_set_tracer_tracking(OrcSolver *s, OrcTracers *t, const OrcTracerSettings *c, uint32_t substeps_per_step) {
@@ -398,35 +375,22 @@ int orc_solver_set_tracer_tracking(OrcSolver *s, OrcTracers *t, const OrcTracerS
     if (c->step_mode != ORC_TRACER_STEP_TIME) return set_error(ORC_ERR_BAD_ARGUMENT, "tracer tracking: the step mode must be TIME");
     if (c->direction != 1) return set_error(ORC_ERR_BAD_ARGUMENT, "tracer tracking: the direction must be +1");
     if (substeps_per_step == 0) return set_error(ORC_ERR_BAD_ARGUMENT, "tracer tracking: substeps_per_step must be at least 1");
-    DevBuf<int> status;
-    ORC_TRY(status.alloc(1));
-    ORC_TRY(status.zero());
+    TracerTracking T;
     if (c->interpolation == ORC_PROBE_LINEAR) {  // one evaluation at the particles first: what the gradient bodies refuse is refused here
-        DevBuf<double> tmp;
-        ORC_TRY(tmp.alloc(3 * (size_t)t->n));
         const TracerState &A = t->st[t->cur];
-        ORC_TRY(probes_launch_sample(st, A.cell.p, A.off.p, t->n, kVelocityMask, ORC_PROBE_LINEAR, tmp.p, status.p));
-        int hs = 0;
-        ORC_TRY(status.download(&hs, 1));
-        ORC_TRY(probes_sample_status(hs));
+        ORC_TRY(sample_to_host(st, A.cell.p, A.off.p, t->n, kVelocityMask, ORC_PROBE_LINEAR, nullptr, nullptr, &T.status));
+    } else {
+        ORC_TRY(T.status.alloc(1));
+        ORC_TRY(T.status.zero());
     }
-    int *raw = nullptr;
-    hipEvent_t ev = nullptr;
-    ORC_HIP(hipHostMalloc((void **)&raw, sizeof(int), hipHostMallocDefault));
-    *raw = 0;
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipHostFree(raw);
-        return set_error(ORC_ERR_HIP, "tracer tracking: hipEventCreate failed");
-    }
-    SolverState::TracerTracking &T = st.tt;
-    T.clear();
-    T.status = std::move(status);
-    T.raw = raw;
-    T.copied = ev;
+    ORC_TRY(T.raw.create(1, "tracer tracking"));
+    *T.raw.host.p = 0;
     T.set = t;
     T.c = *c;
     T.substeps = substeps_per_step;
     T.on = true;
+    st.tt.clear();
+    st.tt = std::move(T);
     return ORC_OK;
 }
 
@@ -443,22 +407,14 @@ int orc_bench_tracers(OrcSolver *s, const OrcTracers *t, const OrcTracerSettings
     ORC_TRY(status.zero());
     const double step = (double)c->direction * c->step;
     const TracerView in = view(t->st[t->cur]), out = view(scratch);
-    hipEvent_t e0, e1;
-    ORC_HIP(hipEventCreate(&e0));
-    ORC_HIP(hipEventCreate(&e1));
-    int rc = launch_advect(st, *c, step, in, out, t->n, n_substeps, nullptr, nullptr, status.p);  // warm-up
-    if (rc == ORC_OK && hipEventRecord(e0, ctx().stream) != hipSuccess) rc = set_error(ORC_ERR_HIP, "hipEventRecord failed");
-    for (int i = 0; i < reps && rc == ORC_OK; ++i) rc = launch_advect(st, *c, step, in, out, t->n, n_substeps, nullptr, nullptr, status.p);
     float ms = 0.f;
-    if (rc == ORC_OK && (hipEventRecord(e1, ctx().stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = set_error(ORC_ERR_HIP, "timing the tracer launches failed");
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    const int rc = timed(reps, [&] { return launch_advect(st, *c, step, in, out, t->n, n_substeps, nullptr, nullptr, status.p); }, &ms,
+                         "timing the tracer launches failed");
     int hs = 0;
     ORC_TRY(status.download(&hs, 1));  // synchronises: the scratch is freed on return
     ORC_TRY(rc);
-    ORC_TRY(probes_sample_status(hs));
-    *avg_ms = (double)ms / reps;
+    ORC_TRY(sample_status(hs));
+    *avg_ms = (double)ms;
     return ORC_OK;
 }
 
